@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's configuration.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (configs[1]): one 8192x8192 int16 plane per GPU per step, forward + inverse 8x8 DCT in ONE fused
 kernel (4 algorithmic bytes per pixel: 2 in + 2 out).  Four distinct plane pairs (1 GiB) are rotated so that no
@@ -14,7 +14,8 @@ The LAST stdout line is one short JSON object (`build_line`, < 4 KB: the driver 
 fused round-trip kernel, timed with HIP events on the launch stream; `kernels` holds one number-only entry per
 other kernel / configuration; `cpu_baseline` is bench_cpu.py.  Everything verbose -- sources, how each figure
 was verified, the issue-floor model, the all-gather leg -- goes to bench_extras.json next to this file
-(bench_extras.py) and to stderr.
+(bench_extras.py) and to stderr.  `--dump-outputs DIR` writes a fixed, seeded sample of what the last timed step
+computed to DIR/roundtrip_i16.npy (float32, 32 MiB), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -36,6 +37,26 @@ METRIC = "Mpixels/s 8x8 fwd+inv int16 DCT, 8192x8192 plane"
 GATHER_TIMEOUT_S = float(os.environ.get("MDCT_BENCH_GATHER_TIMEOUT", "300"))  # watchdog of the optional all-gather legs
 EXTRAS_FILE = os.environ.get("MDCT_BENCH_EXTRAS_FILE", os.path.join(ROOT, "bench_extras.json"))
 LINE_LIMIT = 4096
+DUMP_SAMPLES = W * H // 8  # 8 M elements, 32 MiB as float32
+DUMP_SEED = 20261015
+
+
+def dump_sample_index(n, k=DUMP_SAMPLES, seed=DUMP_SEED):
+    """fixed, seeded positions into a flat output of n elements: one per stride n // k, at a seeded offset inside it (the whole plane
+    is covered evenly; the same positions in every run and every build)"""
+    import numpy as np
+
+    stride = n // k
+    return np.arange(k, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, size=k, dtype=np.int64)
+
+
+def dump_outputs(outdir, arrays):
+    """write {name: host array} as outdir/<name>.npy"""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def build_line(m):
@@ -112,7 +133,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL (default).  gloo only rehearses the multi-rank control flow on a box with fewer GPUs than ranks.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32: a fixed, seeded "
+                         f"sample of {DUMP_SAMPLES} elements of the output plane (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch(args, sys.argv[1:])
@@ -215,6 +241,11 @@ def main():
     barrier()
     wall, kernel_ms = clocked(args.steps)
     torch.cuda.synchronize()
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the output plane of the last timed step, taken before anything else reuses the buffers
+        last = dsts[(args.steps - 1) % NSETS].view(-1)
+        idx = torch.from_numpy(dump_sample_index(last.numel())).to(last.device)
+        dumped = {"roundtrip_i16": last[idx].to(torch.float32).cpu().numpy()}
     if dist is not None:
         dist.barrier()
         torch.cuda.synchronize()
@@ -231,6 +262,9 @@ def main():
         m["wall_s"] = wall = max(float(e[0]) for e in every)
         m["kernel_ms"] = kernel_ms = max(float(e[1]) for e in every)
     log(f"timed region done: {wall / args.steps * 1e3:.4f} ms/step")
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
+        log(f"outputs written to {args.dump_outputs}")
 
     verbose = {}
     try:

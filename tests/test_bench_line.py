@@ -137,3 +137,19 @@ def test_mt_timing_harness_transforms_the_whole_plane():
         rc = lib.orc_time_q32_mt(ctypes.cast(lib.orc_q32_avx, ctypes.c_void_p), -1, img.ctypes.data, got.ctypes.data, lut.ctypes.data_as(O.f32p), Wd, Hd, nthreads, pin, len(cpus), 1, 4, sec)
         assert rc == nthreads and np.array_equal(got, want) and all(s > 0 for s in sec)
     assert lib.orc_time_q32_mt(None, -1, img.ctypes.data, want.ctypes.data, lut.ctypes.data_as(O.f32p), Wd, Hd, 1, pin, len(cpus), 1, 4, sec) == -1
+
+
+def test_dump_sample_is_fixed_in_bounds_and_small(tmp_path):
+    """--dump-outputs: the same positions in every run, all inside the plane, one per stride, and at most 64 MB as float32"""
+    import numpy as np
+
+    n = bench.W * bench.H
+    idx = bench.dump_sample_index(n)
+    assert np.array_equal(idx, bench.dump_sample_index(n))
+    assert idx.size == bench.DUMP_SAMPLES and idx.min() >= 0 and idx.max() < n
+    assert np.array_equal(idx // (n // bench.DUMP_SAMPLES), np.arange(idx.size))
+    assert idx.size * 4 <= 64 * 2**20
+    plane = np.arange(n, dtype=np.int16)
+    bench.dump_outputs(str(tmp_path / "out"), {"roundtrip_i16": plane[idx].astype(np.float32)})
+    back = np.load(tmp_path / "out" / "roundtrip_i16.npy")
+    assert back.dtype == np.float32 and np.array_equal(back, plane[idx].astype(np.float32))

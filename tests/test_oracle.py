@@ -1,6 +1,7 @@
 """CPU tests: the oracle is pinned against (i) fixtures produced by the real reference,
-(ii) the survey's SHA-256 known answers, (iii) the real reference itself when oracle/_ref
-exists (build container only), and its engine-own parts against a double-precision DCT."""
+(ii) the survey's SHA-256 known answers, (iii) the real reference's output hashes on random, extreme, per-tier
+and property-based cases (tests/golden/ref_pins.json), and the real reference itself when oracle/_ref exists,
+and its engine-own parts against a double-precision DCT."""
 import hashlib
 import json
 import os
@@ -13,6 +14,9 @@ from simd_dct_amd import synth
 from simd_dct_amd.api import QUANTIZE_BASE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The real reference (where oracle/_ref exists) is loaded at collection, before any test loads libmdct_hip.so: that library exports
+# the reference's public symbols, and loaded first it would bind the reference's own dispatcher calls to the engine's.
+O.reference()
 
 
 def test_oracle_matches_reference_fixtures(golden):
@@ -63,77 +67,139 @@ def test_oracle_survey_known_answers():
         assert hashlib.sha256(out.tobytes()).hexdigest() == c["sha256"], c
 
 
-@pytest.mark.skipif(O.reference() is None, reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("beh", list(O.REF_FUNCS))
-def test_oracle_equals_real_reference_random(beh):
+PINS_FILE = os.path.join(ROOT, "tests", "golden", "ref_pins.json")
+_pins_cache = []
+
+
+def _sha(a):
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+def _pins():
+    if not _pins_cache:
+        with open(PINS_FILE) as f:
+            _pins_cache.append(json.load(f))
+    return _pins_cache[0]
+
+
+def reference_digest(section, key, live):
+    """The real reference's SHA-256 for one case, as pinned in tests/golden/ref_pins.json (tests/golden/make_ref_pins.py).  Where
+    oracle/_ref exists, `live()` runs the real reference and the pin must still be exactly what it writes."""
+    pin = _pins()[section][key]
+    if O.reference() is not None and live is not None:
+        assert _sha(live()) == pin, (section, key)
+    return pin
+
+
+def random_cases():
+    """(W, H, scale, img, lut) of the random differential test, in its fixed draw order"""
     rng = np.random.default_rng(7)
     for (W, H) in ((64, 16), (192, 48), (256, 64)):
         for scale in (0.05, 1.0, 8.0, 100.0, 2000.0):
             img = rng.integers(0, 256, W * H, dtype=np.uint8)
             lut = (QUANTIZE_BASE * np.float32(scale) * rng.uniform(0.5, 2.0, 64).astype(np.float32)).astype(np.float32)
-            for (y0, y1) in ((0, H), (16, 16), (8, H // 2)):
-                a = np.full(W * H, 0x5A, dtype=np.uint8)
-                b = a.copy()
-                O.run_behaviour(beh, img, lut, W, H, y0, y1, out=a)
-                O.run_behaviour(beh, img, lut, W, H, y0, y1, out=b, use_reference=True)
-                assert np.array_equal(a, b), (beh, W, H, scale, y0, y1)
+            yield W, H, scale, img, lut
 
 
-@pytest.mark.skipif(O.reference() is None, reason="oracle/_ref not built (needs /root/reference)")
-def test_oracle_equals_real_reference_extreme_tables():
-    """cvtps_epi32 'integer indefinite' corner (SURVEY.md 2.3-6): tiny, zero, negative, inf, NaN table entries."""
+def random_ranges(H):
+    return ((0, H), (16, 16), (8, H // 2))
+
+
+def extreme_cases():
+    """(special, img, lut): cvtps_epi32 'integer indefinite' corner: tiny, zero, negative, inf, NaN table entries"""
     rng = np.random.default_rng(11)
-    W, H = 64, 16
-    img = rng.integers(0, 256, W * H, dtype=np.uint8)
+    img = rng.integers(0, 256, 64 * 16, dtype=np.uint8)
     img[:64] = 0  # exact-zero coefficients make 0*inf = NaN reachable
     for special in (1e-4, 1e-7, 0.0, -0.3, np.inf, np.nan, 1e-30, 3e38):
         lut = QUANTIZE_BASE.copy()
         lut[::3] = special
-        for beh in O.REF_FUNCS:
-            a = np.zeros(W * H, dtype=np.uint8)
-            b = a.copy()
-            O.run_behaviour(beh, img, lut, W, H, 0, H, out=a)
-            O.run_behaviour(beh, img, lut, W, H, 0, H, out=b, use_reference=True)
-            assert np.array_equal(a, b), (beh, special)
+        yield repr(float(special)), img, lut
 
 
-@pytest.mark.skipif(O.reference() is None, reason="oracle/_ref not built (needs /root/reference)")
-def test_every_reference_tier_and_public_dispatcher_is_pinned():
-    """The tiers nobody calls by default -- q32 AVX-512VL (simd_dct.cpp:1869-2059), stereo SSSE3 / SSE2
-    (:1330-1536, :1106-1327), encq SSSE3 (:1707-1864) -- equal the pinned tier of their family byte for
-    byte, and the three PUBLIC dispatchers (:71-133) after _DetectCPUFeatures() pick exactly those."""
-    flags = O.host_cpu_flags()
+TIER_SAME = {"q32_avx512vl": ("q32_avx2", "q32_avx"), "stereo_ssse3": ("stereo_sse41", "stereo_sse"), "stereo_sse2": ("stereo_sse41", "stereo_sse"),
+             "encq_ssse3": ("encq_sse41", "encq_sse")}
+TIER_PUBLIC = ((0, "q32_avx"), (1, "stereo_sse"), (2, "encq_sse"))  # what the public dispatchers pick on an AVX2 + SSE4.1 host
+
+
+def tier_cases():
+    """(W, H, scale, img, lut) of the tier / dispatcher test, in its fixed draw order"""
     rng = np.random.default_rng(20261003)
-    same = {"q32_avx512vl": ("q32_avx2", "q32_avx"), "stereo_ssse3": ("stereo_sse41", "stereo_sse"), "stereo_sse2": ("stereo_sse41", "stereo_sse"),
-            "encq_ssse3": ("encq_sse41", "encq_sse")}
-    ran = 0
     for (W, H) in ((64, 16), (192, 48), (256, 64)):
         for scale in (1.0, 8.0, 2000.0):
             img = rng.integers(0, 256, W * H, dtype=np.uint8)
             lut = (QUANTIZE_BASE * np.float32(scale) * rng.uniform(0.5, 2.0, 64).astype(np.float32)).astype(np.float32)
-            for (y0, y1) in ((0, H), (16, 32), (8, H // 2)):
-                for tier, (pinned, beh) in same.items():
-                    if O.REF_TIERS[tier][1] not in flags:
-                        continue
-                    a = O.run_tier(tier, img, lut, W, H, y0, y1, out=np.full(W * H, 0x5A, dtype=np.uint8))
-                    b = O.run_tier(pinned, img, lut, W, H, y0, y1, out=np.full(W * H, 0x5A, dtype=np.uint8))
-                    c = np.full(W * H, 0x5A, dtype=np.uint8)
-                    O.run_behaviour(beh, img, lut, W, H, y0, y1, out=c)  # the restatement
-                    assert np.array_equal(a, b) and np.array_equal(a, c), (tier, W, H, scale, y0, y1)
-                    ran += 1
-                # public entry points after feature detection: q32 -> AVX-512VL/AVX2, stereo -> SSE4.1, encq -> SSE4.1
-                if "avx2" in flags and "sse4_1" in flags:
-                    for which, beh in ((0, "q32_avx"), (1, "stereo_sse"), (2, "encq_sse")):
-                        rc, a = O.run_public(which, img, lut, W, H, y0, y1, out=np.full(W * H, 0x5A, dtype=np.uint8))
-                        c = np.full(W * H, 0x5A, dtype=np.uint8)
-                        O.run_behaviour(beh, img, lut, W, H, y0, y1, out=c)
-                        assert rc == 0 and np.array_equal(a, c), ("public", which, W, H, scale, y0, y1)
-    assert ran > 0
-    # dispatcher status codes (simd_dct.cpp:75-76, :117-118): null -> 1, bad shape -> 2
-    img = np.zeros(64 * 16, dtype=np.uint8)
-    assert O.run_public(0, img, QUANTIZE_BASE, 56, 16, 0, 16)[0] == 2
-    assert O.run_public(1, img, QUANTIZE_BASE, 60, 16, 0, 16)[0] == 2
-    assert O.reference().ref_call_public(0, None, img.ctypes.data, O._lut(QUANTIZE_BASE)[1], 64, 16, 0, 16) == 1
+            yield W, H, scale, img, lut
+
+
+def tier_ranges(H):
+    return ((0, H), (16, 32), (8, H // 2))
+
+
+def case_key(*parts):
+    return "|".join(str(p) for p in parts)
+
+
+@pytest.mark.parametrize("beh", list(O.REF_FUNCS))
+def test_oracle_equals_real_reference_random(beh):
+    for W, H, scale, img, lut in random_cases():
+        for (y0, y1) in random_ranges(H):
+            a = np.full(W * H, 0x5A, dtype=np.uint8)
+            O.run_behaviour(beh, img, lut, W, H, y0, y1, out=a)
+            live = lambda: O.run_behaviour(beh, img, lut, W, H, y0, y1, out=np.full(W * H, 0x5A, dtype=np.uint8), use_reference=True)[1]
+            assert _sha(a) == reference_digest("random", case_key(beh, f"{W}x{H}", scale, y0, y1), live), (beh, W, H, scale, y0, y1)
+
+
+def test_oracle_equals_real_reference_extreme_tables():
+    """cvtps_epi32 'integer indefinite' corner (SURVEY.md 2.3-6): tiny, zero, negative, inf, NaN table entries."""
+    W, H = 64, 16
+    for special, img, lut in extreme_cases():
+        for beh in O.REF_FUNCS:
+            a = np.zeros(W * H, dtype=np.uint8)
+            O.run_behaviour(beh, img, lut, W, H, 0, H, out=a)
+            live = lambda: O.run_behaviour(beh, img, lut, W, H, 0, H, out=np.zeros(W * H, dtype=np.uint8), use_reference=True)[1]
+            assert _sha(a) == reference_digest("extreme", case_key(beh, special), live), (beh, special)
+
+
+def test_every_reference_tier_and_public_dispatcher_is_pinned():
+    """The tiers nobody calls by default -- q32 AVX-512VL (simd_dct.cpp:1869-2059), stereo SSSE3 / SSE2
+    (:1330-1536, :1106-1327), encq SSSE3 (:1707-1864) -- equal the pinned tier of their family byte for
+    byte, and the three PUBLIC dispatchers (:71-133) after _DetectCPUFeatures() pick exactly those.
+    Each tier's bytes are the reference's as pinned in tests/golden/ref_pins.json; where oracle/_ref exists
+    they are also produced live, for every tier this host's CPU can run."""
+    flags = O.host_cpu_flags()
+    canary = lambda W, H: np.full(W * H, 0x5A, dtype=np.uint8)
+    ran = 0
+    for W, H, scale, img, lut in tier_cases():
+        for (y0, y1) in tier_ranges(H):
+            geom = (f"{W}x{H}", scale, y0, y1)
+
+            def tier_digest(tier):
+                flag = O.REF_TIERS[tier][1]
+                live = (lambda: O.run_tier(tier, img, lut, W, H, y0, y1, out=canary(W, H))) if flag is None or flag in flags else None
+                return reference_digest("tiers", case_key(tier, *geom), live)
+
+            for tier, (pinned, beh) in TIER_SAME.items():
+                c = canary(W, H)
+                O.run_behaviour(beh, img, lut, W, H, y0, y1, out=c)  # the restatement
+                assert tier_digest(tier) == tier_digest(pinned) == _sha(c), (tier, W, H, scale, y0, y1)
+                ran += 1
+            # public entry points after feature detection: q32 -> AVX-512VL/AVX2, stereo -> SSE4.1, encq -> SSE4.1
+            for which, beh in TIER_PUBLIC:
+                def live():
+                    rc, out = O.run_public(which, img, lut, W, H, y0, y1, out=canary(W, H))
+                    assert rc == 0
+                    return out
+                c = canary(W, H)
+                O.run_behaviour(beh, img, lut, W, H, y0, y1, out=c)
+                pub_live = live if "avx2" in flags and "sse4_1" in flags else None
+                assert reference_digest("public", case_key(which, *geom), pub_live) == _sha(c), ("public", which, W, H, scale, y0, y1)
+    assert ran == 3 * 3 * 3 * len(TIER_SAME)
+    if O.reference() is not None:
+        # dispatcher status codes (simd_dct.cpp:75-76, :117-118): null -> 1, bad shape -> 2
+        img = np.zeros(64 * 16, dtype=np.uint8)
+        assert O.run_public(0, img, QUANTIZE_BASE, 56, 16, 0, 16)[0] == 2
+        assert O.run_public(1, img, QUANTIZE_BASE, 60, 16, 0, 16)[0] == 2
+        assert O.reference().ref_call_public(0, None, img.ctypes.data, O._lut(QUANTIZE_BASE)[1], 64, 16, 0, 16) == 1
 
 
 def test_argument_errors_match_reference_codes():
@@ -314,36 +380,62 @@ def test_u8_i16_pair_against_double():
     assert (O.u8_i16("inv", wild, 8, 8) == 0).all()
 
 
-@pytest.mark.skipif(O.reference() is None, reason="oracle/_ref not built (needs /root/reference)")
-def test_oracle_equals_real_reference_property_based():
-    """hypothesis-driven differential test of the restatement against the real reference: arbitrary geometry
-    (multiples of the tier's block size), arbitrary row ranges incl. inverted and out-of-range ones, tables over
-    eight decades, constant / random / extreme planes; canary-filled outputs compared in full"""
-    hyp = pytest.importorskip("hypothesis")
-    st = pytest.importorskip("hypothesis.strategies")
+def property_case(beh, gw, gh, y0, y1, logscale, kind, seed):
+    """(W, H, img, lut) of one property-based case"""
+    W, H = gw * 64, gh * 16
+    rng = np.random.default_rng(seed)
+    if kind == 0:
+        img = rng.integers(0, 256, W * H, dtype=np.uint8)
+    elif kind == 1:
+        img = np.full(W * H, rng.integers(0, 256), dtype=np.uint8)
+    elif kind == 2:
+        img = rng.choice(np.array([0, 255], dtype=np.uint8), W * H)
+    else:
+        img = synth.plane_u8_np(W, H, "photo", seed=seed).reshape(-1)
+    lut = (QUANTIZE_BASE * np.float32(10.0 ** logscale) * rng.uniform(0.25, 4.0, 64).astype(np.float32)).astype(np.float32)
+    return W, H, img, lut
 
+
+def property_check(beh, gw, gh, y0, y1, logscale, kind, seed, digest):
+    """the restatement's canary-filled output against `digest(W, H, img, lut)`, the reference's SHA-256 for the case"""
+    W, H, img, lut = property_case(beh, gw, gh, y0, y1, logscale, kind, seed)
+    a = np.full(W * H, 0xC3, dtype=np.uint8)
+    O.run_behaviour(beh, img, lut, W, H, y0, y1, out=a)
+    assert _sha(a) == digest(W, H, img, lut), (beh, W, H, y0, y1, logscale, kind, seed)
+
+
+def property_strategy_check(hyp, st, check):
     @hyp.settings(max_examples=150, deadline=None, derandomize=True, suppress_health_check=list(hyp.HealthCheck))
     @hyp.given(beh=st.sampled_from(sorted(O.REF_FUNCS)), gw=st.integers(1, 6), gh=st.integers(1, 6), y0=st.integers(0, 200), y1=st.integers(0, 300),
                logscale=st.floats(-3.0, 5.0), kind=st.integers(0, 3), seed=st.integers(0, 2**31 - 1))
-    def check(beh, gw, gh, y0, y1, logscale, kind, seed):
-        W, H = gw * 64, gh * 16
-        rng = np.random.default_rng(seed)
-        if kind == 0:
-            img = rng.integers(0, 256, W * H, dtype=np.uint8)
-        elif kind == 1:
-            img = np.full(W * H, rng.integers(0, 256), dtype=np.uint8)
-        elif kind == 2:
-            img = rng.choice(np.array([0, 255], dtype=np.uint8), W * H)
-        else:
-            img = synth.plane_u8_np(W, H, "photo", seed=seed).reshape(-1)
-        lut = (QUANTIZE_BASE * np.float32(10.0 ** logscale) * rng.uniform(0.25, 4.0, 64).astype(np.float32)).astype(np.float32)
-        a = np.full(W * H, 0xC3, dtype=np.uint8)
-        b = a.copy()
-        ra, _ = O.run_behaviour(beh, img, lut, W, H, y0, y1, out=a)
-        rb, _ = O.run_behaviour(beh, img, lut, W, H, y0, y1, out=b, use_reference=True)
-        assert np.array_equal(a, b), (beh, W, H, y0, y1, logscale, kind, seed)
+    def run(**case):
+        check(**case)
 
-    check()
+    return run
+
+
+def test_oracle_equals_real_reference_property_based():
+    """differential test of the restatement against the real reference on hypothesis-drawn cases: arbitrary geometry
+    (multiples of the tier's block size), arbitrary row ranges incl. inverted and out-of-range ones, tables over
+    eight decades, constant / random / extreme planes; canary-filled outputs compared in full.  The cases hypothesis drew
+    against the reference and the reference's output hashes are pinned in tests/golden/ref_pins.json and replayed here;
+    where oracle/_ref exists, hypothesis also draws afresh against the live reference."""
+    cases = _pins()["property"]
+    assert len(cases) >= 150
+    for c in cases:
+        case = {k: v for k, v in c.items() if k != "sha256"}
+        property_check(**case, digest=lambda W, H, img, lut: c["sha256"])
+    if O.reference() is None:
+        return
+    hyp = pytest.importorskip("hypothesis")
+    st = pytest.importorskip("hypothesis.strategies")
+
+    def live(beh, gw, gh, y0, y1, logscale, kind, seed):
+        def digest(W, H, img, lut):
+            return _sha(O.run_behaviour(beh, img, lut, W, H, y0, y1, out=np.full(W * H, 0xC3, dtype=np.uint8), use_reference=True)[1])
+        property_check(beh, gw, gh, y0, y1, logscale, kind, seed, digest)
+
+    property_strategy_check(hyp, st, live)()
 
 
 def test_fma_clone_and_libm_fmaf_build_agree(tmp_path):
