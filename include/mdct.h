@@ -412,6 +412,16 @@ enum
 };
 int mdct_table_cache_stats(uint64_t *stats, int n);
 
+/* Launch tally (diagnostics): how many times the host launched each kernel instantiation, process-wide (all devices, all threads),
+ * since the process started or the last mdct_kernel_counts_reset.  Writes up to n (name, count) pairs of the instantiations whose
+ * count is non-zero and returns how many there are (may exceed n), or -MDCT_INVALID_PARAMETER.  A name is the instantiation as a demangler prints the kernel's
+ * symbol, without namespace, return type or parameter list, e.g. "k_fwd_quant_u8<1, 3, true, true>"; it points to library-owned
+ * storage that lives as long as the process.  Host function, no device work.  Counting costs one relaxed atomic increment per launch
+ * (no lock, no allocation) and is safe inside stream capture: it counts the launches the host records, a replayed graph counts
+ * nothing.  Counts are not ordered with respect to concurrent launches on other threads. */
+int mdct_kernel_counts(const char **names, uint64_t *counts, int n);
+void mdct_kernel_counts_reset(void);
+
 /* Shader-clock probe (diagnostics): `waves` one-wave workgroups each spin for `ticks_100MHz` ticks of the constant 100 MHz counter and write
  * (shader cycles elapsed, ticks elapsed) to out[2 * w], out[2 * w + 1] (device memory, 16 * waves bytes).  Launched on a second stream
  * beside a workload it reports the clock the chip holds under that workload: cycles * 100 / ticks MHz.  ticks_100MHz <= 10^7 (0.1 s). */

@@ -624,6 +624,25 @@ def table_cache_stats():
     return dict(zip(("hits", "uploads", "evictions", "from_arguments", "stream_waits", "unfenceable"), [int(v) for v in a]))
 
 
+def kernel_counts():
+    """mdct_kernel_counts: {instantiation name: host launches since the process started or the last kernel_counts_reset()}"""
+    lib = _lib.load()
+    n = lib.mdct_kernel_counts(None, None, 0)
+    if n < 0:
+        _check(-n)
+    while True:
+        names, counts = (ctypes.c_char_p * max(n, 1))(), (ctypes.c_uint64 * max(n, 1))()
+        m = lib.mdct_kernel_counts(names, counts, n)
+        if m <= n:
+            return {names[i].decode(): int(counts[i]) for i in range(m)}
+        n = m  # another thread launched a new instantiation in between
+
+
+def kernel_counts_reset():
+    """mdct_kernel_counts_reset"""
+    _lib.load().mdct_kernel_counts_reset()
+
+
 def clock_probe(out, ticks_100MHz, waves=8, stream=None):
     """mdct_clock_probe: `out` = int64 device tensor of 2 * waves entries (shader cycles, 100 MHz ticks) per wave"""
     _check(_lib.load().mdct_clock_probe(_ptr(out), int(ticks_100MHz), int(waves), _stream(stream)))

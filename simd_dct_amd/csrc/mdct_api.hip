@@ -10,6 +10,10 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <cxxabi.h>
+#include <dlfcn.h>
+#include <cstdlib>
+#include <string>
 #include <mutex>
 #include <type_traits>
 #include <unordered_map>
@@ -1294,6 +1298,56 @@ static int gen_planes(const mdct_plane_u8_i16 *planes, int n, bool fwd, std::vec
   return MDCT_SUCCESS;
 }
 
+namespace mdct
+{
+TallySlot g_tally[kTallySlots];
+}
+
+namespace
+{
+// "void mdct::k_fwd_quant_u8<1, 3, true, true>(mdct::U8Args)" -> "k_fwd_quant_u8<1, 3, true, true>": the kernel handle's symbol,
+// demangled, without return type, namespace and parameter list.  Resolved once per slot, on the query path.
+std::mutex g_tally_mu;
+const char *g_tally_names[mdct::kTallySlots];
+
+const char *tally_name(size_t slot, const void *kernel)
+{
+  std::lock_guard<std::mutex> lk(g_tally_mu);
+  if (g_tally_names[slot] != nullptr)
+    return g_tally_names[slot];
+  std::string name;
+  Dl_info info;
+  if (dladdr(kernel, &info) != 0 && info.dli_sname != nullptr && info.dli_saddr == kernel)
+  {
+    int st = 0;
+    char *d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &st);
+    name = st == 0 && d != nullptr ? d : info.dli_sname;
+    std::free(d);
+    if (name.compare(0, 5, "void ") == 0)
+      name.erase(0, 5);
+    const size_t paren = name.find('(');
+    if (paren != std::string::npos)
+      name.resize(paren);
+    const size_t tmpl = name.find('<');
+    const size_t ns = name.rfind("::", tmpl);
+    if (ns != std::string::npos)
+      name.erase(0, ns + 2);
+  }
+  else
+  {
+    char buf[32];
+    std::snprintf(buf, sizeof buf, "<kernel %p>", kernel);
+    name = buf;
+  }
+  char *keep = static_cast<char *>(std::malloc(name.size() + 1)); // lives as long as the process (one per instantiation)
+  if (keep == nullptr)
+    return "<out of memory>";
+  std::memcpy(keep, name.c_str(), name.size() + 1);
+  g_tally_names[slot] = keep;
+  return keep;
+}
+} // namespace
+
 extern "C" {
 
 int mdct_fwd_u8_i16_batch(const mdct_plane_u8_i16 *planes, int n_planes, int level_shift, void *stream)
@@ -1370,6 +1424,34 @@ int mdct_table_cache_stats(uint64_t *stats, int n)
   for (int i = 0; i < n; i++)
     stats[i] = i < MDCT_TABLE_STAT_COUNT ? c.stat[i] : 0;
   return MDCT_SUCCESS;
+}
+
+int mdct_kernel_counts(const char **names, uint64_t *counts, int n)
+{
+  if (n < 0 || (n > 0 && (names == nullptr || counts == nullptr)))
+    return -fail(MDCT_INVALID_PARAMETER, "kernel counts: null output or negative n");
+  int found = 0;
+  for (size_t i = 0; i < mdct::kTallySlots; i++)
+  {
+    const mdct::TallySlot &s = mdct::g_tally[i];
+    const void *k = s.key.load(std::memory_order_relaxed);
+    const uint64_t c = s.count.load(std::memory_order_relaxed);
+    if (k == nullptr || c == 0)
+      continue;
+    if (found < n)
+    {
+      names[found] = tally_name(i, k);
+      counts[found] = c;
+    }
+    found++;
+  }
+  return found;
+}
+
+void mdct_kernel_counts_reset(void)
+{
+  for (size_t i = 0; i < mdct::kTallySlots; i++)
+    mdct::g_tally[i].count.store(0, std::memory_order_relaxed);
 }
 
 int mdct_clock_probe(uint64_t *out, uint32_t ticks_100MHz, uint32_t waves, void *stream)

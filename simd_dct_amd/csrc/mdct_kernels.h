@@ -9,6 +9,7 @@
 
 #include "mdct.h"
 #include "batch_plan.h"
+#include "launch_tally.h"
 
 namespace mdct
 {

@@ -2506,20 +2506,29 @@ static inline uint32_t grid_for(uint32_t nblocks) { return (nblocks + kWG - 1) /
 template <int PROFILE, int LAYOUT>
 static hipError_t launch_u8_pl(const U8Args &a, bool safe, hipStream_t s)
 {
+  // the scalar tiers never take the SAFE form (launch_fwd_quant_u8 passes false): not instantiating it keeps dead kernels out of the
+  // code object
+  constexpr bool kHasSafe = PROFILE != MDCT_PROFILE_REF_SCALAR;
   const uint32_t launch_rows = a.nblocks / a.bpr; // rows of blocks in the launch: (block row, eye) pairs for STEREO
   if (a.bpr % kWG == 0 && launch_rows <= 65535u && a.out_tight)
   { // every workgroup inside one row of blocks: 2-D grid, wave-uniform addressing (TILED)
     const dim3 g(a.bpr / kWG, launch_rows);
-    if (safe)
-      hipLaunchKernelGGL((k_fwd_quant_u8<PROFILE, LAYOUT, true, true>), g, dim3(kWG), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_fwd_quant_u8<PROFILE, LAYOUT, false, true>), g, dim3(kWG), 0, s, a);
+    if constexpr (kHasSafe)
+      if (safe)
+      {
+        MDCT_LAUNCH((k_fwd_quant_u8<PROFILE, LAYOUT, true, true>), g, dim3(kWG), 0, s, a);
+        return hipGetLastError();
+      }
+    MDCT_LAUNCH((k_fwd_quant_u8<PROFILE, LAYOUT, false, true>), g, dim3(kWG), 0, s, a);
     return hipGetLastError();
   }
-  if (safe)
-    hipLaunchKernelGGL((k_fwd_quant_u8<PROFILE, LAYOUT, true, false>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_fwd_quant_u8<PROFILE, LAYOUT, false, false>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
+  if constexpr (kHasSafe)
+    if (safe)
+    {
+      MDCT_LAUNCH((k_fwd_quant_u8<PROFILE, LAYOUT, true, false>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
+      return hipGetLastError();
+    }
+  MDCT_LAUNCH((k_fwd_quant_u8<PROFILE, LAYOUT, false, false>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
   return hipGetLastError();
 }
 
@@ -2533,18 +2542,18 @@ hipError_t launch_fwd_quant_u8(const U8Args &a, int layout, int profile, bool sa
     const uint32_t launch_rows = a.nblocks / a.bpr;
     if (!safe && !general && a.bpr % 64 == 0 && launch_rows <= 65535u)
     { // every wave inside one block row: the tile kernel with wave-uniform addressing
-      hipLaunchKernelGGL(k_q32_tile, dim3(a.bpr / 64, launch_rows), dim3(64), 0, s, a);
+      MDCT_LAUNCH(k_q32_tile, dim3(a.bpr / 64, launch_rows), dim3(64), 0, s, a);
       return hipGetLastError();
     }
     const dim3 g(grid_for(a.nblocks)), b(kWG);
     if (safe && general)
-      hipLaunchKernelGGL((k_q32_avx<true, true>), g, b, 0, s, a);
+      MDCT_LAUNCH((k_q32_avx<true, true>), g, b, 0, s, a);
     else if (safe)
-      hipLaunchKernelGGL((k_q32_avx<true, false>), g, b, 0, s, a);
+      MDCT_LAUNCH((k_q32_avx<true, false>), g, b, 0, s, a);
     else if (general)
-      hipLaunchKernelGGL((k_q32_avx<false, true>), g, b, 0, s, a);
+      MDCT_LAUNCH((k_q32_avx<false, true>), g, b, 0, s, a);
     else
-      hipLaunchKernelGGL((k_q32_avx<false, false>), g, b, 0, s, a);
+      MDCT_LAUNCH((k_q32_avx<false, false>), g, b, 0, s, a);
     return hipGetLastError();
   }
   if (layout == MDCT_LAYOUT_STEREO && profile == MDCT_PROFILE_REF_SSE)
@@ -2574,29 +2583,29 @@ static hipError_t launch_i16_m(const I16Args &a, bool has_lut, bool lut_bounded,
     if (has_lut && RT && lut_bounded)
     {
       if (small)
-        hipLaunchKernelGGL((k_i16_tile<MODE, true, !RT, 4>), g, dim3(64), 0, s, a);
+        MDCT_LAUNCH((k_i16_tile<MODE, true, !RT, 4>), g, dim3(64), 0, s, a);
       else
-        hipLaunchKernelGGL((k_i16_tile<MODE, true, !RT, 2>), g, dim3(64), 0, s, a);
+        MDCT_LAUNCH((k_i16_tile<MODE, true, !RT, 2>), g, dim3(64), 0, s, a);
     }
     else if (has_lut)
     {
       if (small)
-        hipLaunchKernelGGL((k_i16_tile<MODE, true, true, 4>), g, dim3(64), 0, s, a);
+        MDCT_LAUNCH((k_i16_tile<MODE, true, true, 4>), g, dim3(64), 0, s, a);
       else
-        hipLaunchKernelGGL((k_i16_tile<MODE, true, true, 2>), g, dim3(64), 0, s, a);
+        MDCT_LAUNCH((k_i16_tile<MODE, true, true, 2>), g, dim3(64), 0, s, a);
     }
     else if (small)
-      hipLaunchKernelGGL((k_i16_tile<MODE, false, true, 4>), g, dim3(64), 0, s, a);
+      MDCT_LAUNCH((k_i16_tile<MODE, false, true, 4>), g, dim3(64), 0, s, a);
     else
-      hipLaunchKernelGGL((k_i16_tile<MODE, false, true, 2>), g, dim3(64), 0, s, a);
+      MDCT_LAUNCH((k_i16_tile<MODE, false, true, 2>), g, dim3(64), 0, s, a);
     return hipGetLastError();
   }
   if (has_lut && RT && lut_bounded)
-    hipLaunchKernelGGL((k_i16<MODE, true, !RT>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
+    MDCT_LAUNCH((k_i16<MODE, true, !RT>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
   else if (has_lut)
-    hipLaunchKernelGGL((k_i16<MODE, true>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
+    MDCT_LAUNCH((k_i16<MODE, true>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
   else
-    hipLaunchKernelGGL((k_i16<MODE, false>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
+    MDCT_LAUNCH((k_i16<MODE, false>), dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
   return hipGetLastError();
 }
 
@@ -2618,19 +2627,19 @@ static hipError_t launch_i16_batch_w(const BatchArgs &a, uint32_t total, int mod
 {
   const dim3 g(total), b(64);
   if (mode == MODE_FWD)
-    hipLaunchKernelGGL((k_i16_batch<MODE_FWD, BATCH_ALL_LUT, true, SMALL>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_i16_batch<MODE_FWD, BATCH_ALL_LUT, true, SMALL>), g, b, 0, s, a);
   else if (mode == MODE_INV)
-    hipLaunchKernelGGL((k_i16_batch<MODE_INV, BATCH_ALL_LUT, true, SMALL>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_i16_batch<MODE_INV, BATCH_ALL_LUT, true, SMALL>), g, b, 0, s, a);
   else if (mode != MODE_ROUNDTRIP)
     return hipErrorInvalidValue;
   else if (lutmode == BATCH_NO_LUT)
-    hipLaunchKernelGGL((k_i16_batch<MODE_ROUNDTRIP, BATCH_NO_LUT, true, SMALL>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_i16_batch<MODE_ROUNDTRIP, BATCH_NO_LUT, true, SMALL>), g, b, 0, s, a);
   else if (lutmode == BATCH_ALL_LUT && !sat)
-    hipLaunchKernelGGL((k_i16_batch<MODE_ROUNDTRIP, BATCH_ALL_LUT, false, SMALL>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_i16_batch<MODE_ROUNDTRIP, BATCH_ALL_LUT, false, SMALL>), g, b, 0, s, a);
   else if (lutmode == BATCH_ALL_LUT)
-    hipLaunchKernelGGL((k_i16_batch<MODE_ROUNDTRIP, BATCH_ALL_LUT, true, SMALL>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_i16_batch<MODE_ROUNDTRIP, BATCH_ALL_LUT, true, SMALL>), g, b, 0, s, a);
   else
-    hipLaunchKernelGGL((k_i16_batch<MODE_ROUNDTRIP, BATCH_MIXED, true, SMALL>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_i16_batch<MODE_ROUNDTRIP, BATCH_MIXED, true, SMALL>), g, b, 0, s, a);
   return hipGetLastError();
 }
 
@@ -2646,9 +2655,9 @@ static hipError_t launch_u8_batch_m(const BatchArgs &a, uint32_t total, hipStrea
 {
   const dim3 g(total), b(64);
   if (total > 2048 && total <= kTileSmallLaunch)
-    hipLaunchKernelGGL((k_u8_batch<MODE, GENERAL, true>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_u8_batch<MODE, GENERAL, true>), g, b, 0, s, a);
   else
-    hipLaunchKernelGGL((k_u8_batch<MODE, GENERAL, false>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_u8_batch<MODE, GENERAL, false>), g, b, 0, s, a);
   return hipGetLastError();
 }
 
@@ -2657,9 +2666,9 @@ hipError_t launch_q32_batch(const BatchArgs &a, uint32_t total, bool safe, hipSt
   if (total == 0)
     return hipSuccess;
   if (safe)
-    hipLaunchKernelGGL(k_q32_batch<true>, dim3(total), dim3(64), 0, s, a);
+    MDCT_LAUNCH(k_q32_batch<true>, dim3(total), dim3(64), 0, s, a);
   else
-    hipLaunchKernelGGL(k_q32_batch<false>, dim3(total), dim3(64), 0, s, a);
+    MDCT_LAUNCH(k_q32_batch<false>, dim3(total), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -2690,13 +2699,13 @@ hipError_t preload_kernels()
 
 hipError_t launch_clock_probe(unsigned long long *out, unsigned int ticks, unsigned int waves, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_clock_probe, dim3(waves), dim3(64), 0, s, out, ticks);
+  MDCT_LAUNCH(k_clock_probe, dim3(waves), dim3(64), 0, s, out, ticks);
   return hipGetLastError();
 }
 
 hipError_t launch_park_table(const OwnTables &tb, OwnTables *slot, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_park_table, dim3(1), dim3(64), 0, s, tb, slot);
+  MDCT_LAUNCH(k_park_table, dim3(1), dim3(64), 0, s, tb, slot);
   return hipGetLastError();
 }
 
@@ -2704,7 +2713,7 @@ hipError_t launch_u8_i16_fwd(const U8I16Args &a, hipStream_t s)
 {
   if (a.nblocks == 0)
     return hipSuccess;
-  hipLaunchKernelGGL(k_u8_i16_fwd, dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
+  MDCT_LAUNCH(k_u8_i16_fwd, dim3(grid_for(a.nblocks)), dim3(kWG), 0, s, a);
   return hipGetLastError();
 }
 
@@ -2713,11 +2722,11 @@ hipError_t launch_u8_records(const U8RecArgs &a, bool i16_in, hipStream_t s, boo
   if (a.nblocks == 0)
     return hipSuccess;
   if (i16_in)
-    hipLaunchKernelGGL(k_u8_records<true>, dim3((a.nblocks + 63) / 64), dim3(64), 0, s, a);
+    MDCT_LAUNCH(k_u8_records<true>, dim3((a.nblocks + 63) / 64), dim3(64), 0, s, a);
   else if (clamp)
-    hipLaunchKernelGGL(k_u8_records<false>, dim3((a.nblocks + 63) / 64), dim3(64), 0, s, a);
+    MDCT_LAUNCH(k_u8_records<false>, dim3((a.nblocks + 63) / 64), dim3(64), 0, s, a);
   else
-    hipLaunchKernelGGL((k_u8_records<false, false>), dim3((a.nblocks + 63) / 64), dim3(64), 0, s, a);
+    MDCT_LAUNCH((k_u8_records<false, false>), dim3((a.nblocks + 63) / 64), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -2731,23 +2740,23 @@ hipError_t launch_px_huffman(const PxHuffArgs &a, bool i16_in, bool pack, bool c
   if (i16_in)
   {
     if (pack)
-      hipLaunchKernelGGL((k_px_huffman_rows<true, 4, true>), grid, wg, 0, s, a);
+      MDCT_LAUNCH((k_px_huffman_rows<true, 4, true>), grid, wg, 0, s, a);
     else
-      hipLaunchKernelGGL((k_px_huffman_rows<true, 4, false>), grid, wg, 0, s, a);
+      MDCT_LAUNCH((k_px_huffman_rows<true, 4, false>), grid, wg, 0, s, a);
   }
   else if (clamp)
   {
     if (pack)
-      hipLaunchKernelGGL((k_px_huffman_rows<false, 4, true>), grid, wg, 0, s, a);
+      MDCT_LAUNCH((k_px_huffman_rows<false, 4, true>), grid, wg, 0, s, a);
     else
-      hipLaunchKernelGGL((k_px_huffman_rows<false, 4, false>), grid, wg, 0, s, a);
+      MDCT_LAUNCH((k_px_huffman_rows<false, 4, false>), grid, wg, 0, s, a);
   }
   else
   {
     if (pack)
-      hipLaunchKernelGGL((k_px_huffman_rows<false, 4, true, false>), grid, wg, 0, s, a);
+      MDCT_LAUNCH((k_px_huffman_rows<false, 4, true, false>), grid, wg, 0, s, a);
     else
-      hipLaunchKernelGGL((k_px_huffman_rows<false, 4, false, false>), grid, wg, 0, s, a);
+      MDCT_LAUNCH((k_px_huffman_rows<false, 4, false, false>), grid, wg, 0, s, a);
   }
   return hipGetLastError();
 }
@@ -2762,20 +2771,20 @@ hipError_t launch_f32(const F32Args &a, int mode, hipStream_t s)
   {
     const dim3 g2(a.bpr / 64, launch_rows);
     if (mode == MODE_FWD)
-      hipLaunchKernelGGL(k_f32_tile<MODE_FWD>, g2, dim3(64), 0, s, a);
+      MDCT_LAUNCH(k_f32_tile<MODE_FWD>, g2, dim3(64), 0, s, a);
     else
-      hipLaunchKernelGGL(k_f32_tile<MODE_INV>, g2, dim3(64), 0, s, a);
+      MDCT_LAUNCH(k_f32_tile<MODE_INV>, g2, dim3(64), 0, s, a);
     return hipGetLastError();
   }
   const dim3 g(grid_for(a.nblocks)), b(kWG);
   if (mode == MODE_FWD && wide)
-    hipLaunchKernelGGL((k_f32<MODE_FWD, true>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_f32<MODE_FWD, true>), g, b, 0, s, a);
   else if (mode == MODE_FWD)
-    hipLaunchKernelGGL((k_f32<MODE_FWD, false>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_f32<MODE_FWD, false>), g, b, 0, s, a);
   else if (wide)
-    hipLaunchKernelGGL((k_f32<MODE_INV, true>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_f32<MODE_INV, true>), g, b, 0, s, a);
   else
-    hipLaunchKernelGGL((k_f32<MODE_INV, false>), g, b, 0, s, a);
+    MDCT_LAUNCH((k_f32<MODE_INV, false>), g, b, 0, s, a);
   return hipGetLastError();
 }
 
@@ -2787,7 +2796,7 @@ hipError_t launch_stream_copy(const void *from, void *to, size_t bytes, int cus,
   (void)cus;
   const size_t per_wg = (size_t)kWG * kCopyUnroll;
   const size_t grid = (n16 + per_wg - 1) / per_wg;
-  hipLaunchKernelGGL(k_stream_copy, dim3((uint32_t)grid), dim3(kWG), 0, s, (const u32x4 *)from, (u32x4 *)to, n16);
+  MDCT_LAUNCH(k_stream_copy, dim3((uint32_t)grid), dim3(kWG), 0, s, (const u32x4 *)from, (u32x4 *)to, n16);
   return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 #include "huffman_rows.h"
 #include "pack_rows.h"
 #include "mdct.h"
+#include "launch_tally.h"
 #include "scan_records.h"
 
 extern "C" __attribute__((visibility("hidden"))) int mdct_set_error(int code, const char *fmt, ...); // mdct_api.hip
@@ -536,9 +537,9 @@ int scan_launch(int src, const void *coef, size_t pitch, size_t sizeX, size_t si
   { \
     const dim3 g((uint32_t)((n + mdct::scan_wg(SRC) - 1) / mdct::scan_wg(SRC))), b(mdct::scan_wg(SRC)); \
     if (runs) \
-      hipLaunchKernelGGL((mdct::k_scan<SRC, true>), g, b, 0, s, a); \
+      MDCT_LAUNCH((mdct::k_scan<SRC, true>), g, b, 0, s, a); \
     else \
-      hipLaunchKernelGGL((mdct::k_scan<SRC, false>), g, b, 0, s, a); \
+      MDCT_LAUNCH((mdct::k_scan<SRC, false>), g, b, 0, s, a); \
   } while (0)
   switch (src)
   {
@@ -623,7 +624,7 @@ int mdct_huffman_rows(const int16_t *levels, const uint8_t *runs, const uint8_t 
   a.by0 = (uint32_t)by0;
   huff_build(chroma ? 2 : 0, a.dc, 12);
   huff_build(chroma ? 3 : 1, a.ac, 256);
-  hipLaunchKernelGGL(mdct::k_huffman_rows, dim3((uint32_t)(by1 - by0)), dim3(mdct::kHuffChunk), 0, (hipStream_t)stream, a);
+  MDCT_LAUNCH(mdct::k_huffman_rows, dim3((uint32_t)(by1 - by0)), dim3(mdct::kHuffChunk), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MDCT_SUCCESS : mdct_set_error(MDCT_NOT_SUPPORTED, "huffman kernel launch: %s", hipGetErrorString(e));
 }
@@ -668,14 +669,14 @@ static int pack_rows(const uint8_t *segments, const uint32_t *seg_bytes, const u
   // counted rows, and few enough of them that every workgroup can sum the lengths before its own: one launch
   static const bool never_own = getenv("MDCT_PACK_SCAN_KERNEL") != nullptr;
   if (n_rows && ff_counts && n_rows <= 16384 && !never_own)
-    hipLaunchKernelGGL(mdct::k_pack_write<true>, dim3(a.n_rows), dim3(256), 0, s, a);
+    MDCT_LAUNCH(mdct::k_pack_write<true>, dim3(a.n_rows), dim3(256), 0, s, a);
   else
   {
     if (n_rows && !ff_counts)
-      hipLaunchKernelGGL(mdct::k_pack_count, dim3(a.n_rows), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(mdct::k_pack_scan, dim3(1), dim3(256), 0, s, a);
+      MDCT_LAUNCH(mdct::k_pack_count, dim3(a.n_rows), dim3(256), 0, s, a);
+    MDCT_LAUNCH(mdct::k_pack_scan, dim3(1), dim3(256), 0, s, a);
     if (n_rows)
-      hipLaunchKernelGGL(mdct::k_pack_write<false>, dim3(a.n_rows), dim3(256), 0, s, a);
+      MDCT_LAUNCH(mdct::k_pack_write<false>, dim3(a.n_rows), dim3(256), 0, s, a);
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MDCT_SUCCESS : mdct_set_error(MDCT_NOT_SUPPORTED, "pack kernel launch: %s", hipGetErrorString(e));
@@ -708,9 +709,9 @@ static int run_split420(const uint8_t *ycc, size_t pitch, size_t sizeX, size_t s
   a.nthreads = (uint32_t)n;
   const dim3 grid((uint32_t)((n + mdct::kWG - 1) / mdct::kWG));
   if (u8_out)
-    hipLaunchKernelGGL(mdct::k_split420<true>, grid, dim3(mdct::kWG), 0, (hipStream_t)stream, a);
+    MDCT_LAUNCH(mdct::k_split420<true>, grid, dim3(mdct::kWG), 0, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(mdct::k_split420<false>, grid, dim3(mdct::kWG), 0, (hipStream_t)stream, a);
+    MDCT_LAUNCH(mdct::k_split420<false>, grid, dim3(mdct::kWG), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MDCT_SUCCESS : mdct_set_error(MDCT_NOT_SUPPORTED, "split kernel launch: %s", hipGetErrorString(e));
 }

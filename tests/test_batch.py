@@ -132,9 +132,10 @@ def test_batch_mixed_shapes_match_oracle(cuda, mode):
     """widths that are not multiples of 512 px (partial last tile), one-block planes, shared / distinct / no tables, pitched rows:
     the no-allocation call and the device-table batch give the oracle's planes and leave everything else alone"""
     torch = cuda
-    shapes = [(1920, 64), (8, 8), (72, 24), (520, 16), (256, 24), (200, 40), (3840, 16), (768, 40)]  # the last two and (256, 24): rows ending in half a tile, tiled in pairs
+    # (3840, 16), (768, 40) and (256, 24): rows ending in half a tile, tiled in pairs; (512, 8): whole 64-block tiles (bpr % 64 == 0)
+    shapes = [(1920, 64), (8, 8), (72, 24), (520, 16), (256, 24), (200, 40), (3840, 16), (768, 40), (512, 8)]
     l30, l60 = _lut(30), _lut(60)
-    for luts, pad in (([None] * 8, 0), ([l30, l60, l60, None, l30, _lut(10), None, l60], 24), ([l30] * 8, 8)):
+    for luts, pad in (([None] * 9, 0), ([l30, l60, l60, None, l30, _lut(10), None, l60, l30], 24), ([l30] * 9, 8)):
         for form in ("args", "device"):
             srcs, d_in, d_out, desc = _planes(torch, shapes, luts, pad)
             if form == "args":

@@ -106,6 +106,20 @@ def test_reference_api_matches_oracle(beh):
                 rc2, want = O.run_behaviour(beh, img, lut, W, H, y0, y1, out=want)
                 assert rc == rc2 == 0
                 assert np.array_equal(got, want), (beh, W, H, kind, y0, y1, int((got != want).sum()))
+    # configs[2]'s real widths and widths next to a tile boundary (the TILED forms need a block row of whole 256-block workgroups,
+    # width % 2048 == 0, for stereo / encq; q32's tile form width % 512 == 0), device pointers and, for one width per tier, host pointers
+    widths = (1920, 3840, 7680, 1984, 2112) if beh == "q32_avx" else (1920, 3840, 7680, 2032, 2064, 4080, 4112, 2048, 4096)
+    for W in widths:
+        H = 32
+        img = synth.plane_u8_np(W, H, "noise", seed=synth.SEED + W)
+        lut = (lut_x(2000.0 if beh == "q32_avx" else 8.0) * rng.uniform(0.5, 2.0, 64).astype(np.float32)).astype(np.float32)
+        for (y0, y1) in ((0, H), (16, 32), (8, H // 2)):
+            for host in ((False, True) if W in (1920, 2048) else (False,)):
+                rc, got = run_ref_api(beh, img, lut, W, H, y0, y1, host=host)
+                want = np.full(W * H, CANARY, dtype=np.uint8)
+                rc2, want = O.run_behaviour(beh, img, lut, W, H, y0, y1, out=want)
+                assert rc == rc2 == 0
+                assert np.array_equal(got, want), (beh, W, H, y0, y1, host, int((got != want).sum()))
 
 
 def test_q32_native_ranges_pitch_and_tails():
@@ -148,18 +162,20 @@ def test_unaligned_input_pointer():
 def test_extreme_tables_integer_indefinite_corner():
     """cvtps_epi32 returns 0x80000000 for NaN / out-of-range: exercised with
     zero, tiny, negative, infinite and NaN table entries (the SAFE kernel variant)"""
-    W, H = 64, 32
-    rng = np.random.default_rng(11)
-    img = rng.integers(0, 256, W * H, dtype=np.uint8)
-    img[: W * 8] = 0
-    for special in (1e-4, 1e-7, 0.0, -0.3, np.inf, np.nan, 1e-30, 3e38):
-        lut = M.QUANTIZE_BASE.copy()
-        lut[::3] = special
-        for beh in BEHAVIOURS:
-            rc, got = run_ref_api(beh, img, lut, W, H, 0, H)
-            want = np.full(W * H, CANARY, dtype=np.uint8)
-            O.run_behaviour(beh, img, lut, W, H, 0, H, out=want)
-            assert rc == 0 and np.array_equal(got, want), (beh, special, int((got != want).sum()))
+    # (512, 128) / (2048, 64) / (4096, 32): the SAFE q32 form without a partial wave (k_q32_avx<true, false>) and the SAFE TILED
+    # stereo / encq forms (width % 2048 == 0)
+    for (W, H) in ((64, 32), (512, 128), (2048, 64), (4096, 32)):
+        rng = np.random.default_rng(11)
+        img = rng.integers(0, 256, W * H, dtype=np.uint8)
+        img[: W * 8] = 0
+        for special in (1e-4, 1e-7, 0.0, -0.3, np.inf, np.nan, 1e-30, 3e38):
+            lut = M.QUANTIZE_BASE.copy()
+            lut[::3] = special
+            for beh in BEHAVIOURS:
+                rc, got = run_ref_api(beh, img, lut, W, H, 0, H)
+                want = np.full(W * H, CANARY, dtype=np.uint8)
+                O.run_behaviour(beh, img, lut, W, H, 0, H, out=want)
+                assert rc == 0 and np.array_equal(got, want), (beh, special, W, H, int((got != want).sum()))
 
 
 def test_status_codes_on_device():

@@ -223,9 +223,10 @@ def test_u8_batch_mixed_shapes_and_tables(cuda):
     torch = cuda
     T = _tables()
     # (3840 x 16, 256 x 24, 768 x 40: rows ending in half a tile -- k_u8_batch tiles them over pairs of block rows, the odd last row alone)
-    shapes = [(1920, 64), (8, 8), (72, 24), (520, 16), (256, 24), (200, 40), (3840, 16), (768, 40)]
-    for luts, pad, shift in (([None] * 8, 0, True), ([JPEG_LUMA, JPEG_CHROMA, JPEG_CHROMA, None, JPEG_LUMA, _lut(10), None, T["edge"]], 24, True),
-                             ([JPEG_LUMA, T["tiny"], JPEG_CHROMA, T["huge"], None, T["mixed"], JPEG_LUMA, JPEG_LUMA], 8, False)):
+    # (512, 8): whole 64-block tiles (bpr % 64 == 0)
+    shapes = [(1920, 64), (8, 8), (72, 24), (520, 16), (256, 24), (200, 40), (3840, 16), (768, 40), (512, 8)]
+    for luts, pad, shift in (([None] * 9, 0, True), ([JPEG_LUMA, JPEG_CHROMA, JPEG_CHROMA, None, JPEG_LUMA, _lut(10), None, T["edge"], T["tiny"]], 24, True),
+                             ([JPEG_LUMA, T["tiny"], JPEG_CHROMA, T["huge"], None, T["mixed"], JPEG_LUMA, JPEG_LUMA, JPEG_CHROMA], 8, False)):
         for form in ("args", "device"):
             srcs, d_in, d_out, desc = _u8_planes(torch, shapes, luts, pad)
             if form == "args":
@@ -394,9 +395,10 @@ def test_u8_i16_batches_equal_the_single_plane_calls_and_the_oracle(cuda):
 
     torch = cuda
     T = _tables()
-    shapes = [(1920, 32), (8, 8), (72, 24), (520, 16), (256, 24), (768, 40), (3840, 16)]  # the last three: paired rows (kDescPaired)
+    # (256, 24), (768, 40), (3840, 16): paired rows (kDescPaired); (1024, 32): whole 64-block tiles (bpr % 64 == 0)
+    shapes = [(1920, 32), (8, 8), (72, 24), (520, 16), (256, 24), (768, 40), (3840, 16), (1024, 32)]
     rng = np.random.default_rng(8)
-    for luts, pad, shift in (([None] * 7, 0, True), ([JPEG_LUMA, JPEG_CHROMA, JPEG_CHROMA, None, T["tiny"], _lut(10), T["mixed"]], 16, True), ([T["huge"], JPEG_LUMA, T["ones"], T["sixteenth"], None, T["negative"], T["edge"]], 8, False)):
+    for luts, pad, shift in (([None] * 8, 0, True), ([JPEG_LUMA, JPEG_CHROMA, JPEG_CHROMA, None, T["tiny"], _lut(10), T["mixed"], JPEG_LUMA], 16, True), ([T["huge"], JPEG_LUMA, T["ones"], T["sixteenth"], None, T["negative"], T["edge"], T["ones"]], 8, False)):
         for form in ("args", "device"):
             px_np = [synth.plane_u8_np(w, h, "photo" if i % 2 else "noise", seed=60 + i) for i, (w, h) in enumerate(shapes)]
             px = [torch.from_numpy(np.pad(a, ((0, 0), (0, pad)), constant_values=9)).cuda() for a in px_np]
