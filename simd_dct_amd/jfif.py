@@ -73,3 +73,150 @@ def write_jpeg(components, width, height, specs=None):
         f.append(bytes(memoryview(np.ascontiguousarray(c["scan"]))) if "scan" in c else scan_bytes(c["segments"], c["seg_bytes"], c["seg_stride"]))
     f.append(b"\xff\xd9")
     return b"".join(f)
+
+
+class JpegFormatError(ValueError):
+    """a file this reader refuses: malformed, or outside 8-bit baseline / extended-sequential Huffman JPEG with restart markers"""
+
+
+_SOF_REFUSED = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "hierarchical (SOF5)", 0xC6: "hierarchical progressive (SOF6)",
+                0xC7: "hierarchical lossless (SOF7)", 0xC9: "arithmetic coding (SOF9)", 0xCA: "arithmetic progressive (SOF10)",
+                0xCB: "arithmetic lossless (SOF11)", 0xCD: "arithmetic hierarchical (SOF13)", 0xCE: "arithmetic hierarchical progressive (SOF14)",
+                0xCF: "arithmetic hierarchical lossless (SOF15)", 0xCC: "arithmetic conditioning (DAC)", 0xDC: "DNL"}
+
+
+def _entropy_end(data, i):
+    """offset of the first marker after entropy-coded data starting at i that is neither a stuffed 0xFF nor RSTm"""
+    n = len(data)
+    while True:
+        j = data.find(b"\xff", i)
+        if j < 0 or j + 1 >= n:
+            raise JpegFormatError("entropy-coded data runs to the end of the file (no EOI)")
+        m = data[j + 1]
+        if m == 0x00 or 0xD0 <= m <= 0xD7:
+            i = j + 2
+        elif m == 0xFF:
+            i = j + 1  # fill byte before a marker
+        else:
+            k = j
+            while k > i and data[k - 1] == 0xFF:  # fill bytes belong to the marker
+                k -= 1
+            return k
+
+
+def read_jpeg(data):
+    """Parse a baseline (SOF0) or 8-bit extended-sequential Huffman (SOF1) JPEG with restart markers (ITU-T T.81 B.2).
+    Returns a dict:
+      width, height, sof (0xC0 / 0xC1),
+      components: [{'id', 'h', 'v', 'tq'}] in frame order,
+      qtables: {tq: uint16 [64] natural order (v*8+u)} as last defined,
+      huffman: {(table_class, th): (bits16 list, vals list)} as last defined (class 0 DC, 1 AC),
+      scans: [{'components': [{'index' (into components), 'td', 'ta'}], 'restart_interval', 'start', 'end' (byte range of the
+               entropy-coded data in `data`, stuffed, RSTm included), 'huffman' / 'qtables' (the tables in force at the scan)}]
+    Refuses (JpegFormatError) progressive, lossless, hierarchical and arithmetic-coded files, 12-bit samples, 16-bit DQT, DNL,
+    other than 1 or 3 components, and a scan without a restart interval (no DRI, or DRI 0)."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise JpegFormatError("no SOI")
+    zz = api.zigzag_table()
+    i, n = 2, len(data)
+    frame, qt, ht, dri, scans = None, {}, {}, 0, []
+    while True:
+        while i < n and data[i] == 0xFF and i + 1 < n and data[i + 1] == 0xFF:
+            i += 1  # fill bytes
+        if i + 2 > n or data[i] != 0xFF:
+            raise JpegFormatError(f"expected a marker at offset {i}")
+        m = data[i + 1]
+        if m == 0xD9:
+            break
+        if m in (0x01,) or 0xD0 <= m <= 0xD7:
+            raise JpegFormatError(f"marker 0x{m:02x} outside entropy-coded data")
+        if i + 4 > n:
+            raise JpegFormatError("truncated marker segment")
+        L = struct.unpack_from(">H", data, i + 2)[0]
+        seg = data[i + 4:i + 2 + L]
+        if L < 2 or len(seg) != L - 2:
+            raise JpegFormatError(f"truncated segment 0x{m:02x}")
+        i += 2 + L
+        if m in _SOF_REFUSED:
+            raise JpegFormatError(f"not supported: {_SOF_REFUSED[m]}")
+        if m in (0xC0, 0xC1):
+            if frame is not None:
+                raise JpegFormatError("a second frame header")
+            P, Y, X, nf = struct.unpack_from(">BHHB", seg)
+            if P != 8:
+                raise JpegFormatError(f"not supported: {P}-bit samples (8-bit only)")
+            if nf not in (1, 3):
+                raise JpegFormatError(f"not supported: {nf} components (1 or 3)")
+            if Y == 0:
+                raise JpegFormatError("not supported: height defined by DNL")
+            if X == 0 or len(seg) < 6 + 3 * nf:
+                raise JpegFormatError("malformed frame header")
+            comps = []
+            for c in range(nf):
+                cid, hv, tq = seg[6 + 3 * c:9 + 3 * c]
+                h, v = hv >> 4, hv & 15
+                if h not in (1, 2) or v not in (1, 2) or tq > 3:
+                    raise JpegFormatError(f"not supported: component {cid} sampling {h}x{v} / table {tq}")
+                comps.append(dict(id=cid, h=h, v=v, tq=tq))
+            frame = dict(width=X, height=Y, sof=m, components=comps)
+        elif m == 0xDB:
+            p = 0
+            while p < len(seg):
+                pq, tq = seg[p] >> 4, seg[p] & 15
+                if pq != 0:
+                    raise JpegFormatError("not supported: 16-bit DQT")
+                if tq > 3 or p + 65 > len(seg):
+                    raise JpegFormatError("malformed DQT")
+                q = np.zeros(64, dtype=np.uint16)
+                q[zz] = np.frombuffer(seg[p + 1:p + 65], dtype=np.uint8)
+                qt[tq] = q
+                p += 65
+        elif m == 0xC4:
+            p = 0
+            while p < len(seg):
+                tc, th = seg[p] >> 4, seg[p] & 15
+                if tc > 1 or th > 1:
+                    raise JpegFormatError(f"not supported: Huffman table class {tc} id {th} (two DC and two AC tables)")
+                if p + 17 > len(seg):
+                    raise JpegFormatError("malformed DHT")
+                bits = list(seg[p + 1:p + 17])
+                k = sum(bits)
+                if p + 17 + k > len(seg):
+                    raise JpegFormatError("malformed DHT")
+                ht[(tc, th)] = (bits, list(seg[p + 17:p + 17 + k]))
+                p += 17 + k
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise JpegFormatError("malformed DRI")
+            dri = struct.unpack(">H", seg)[0]
+        elif m == 0xDA:
+            if frame is None:
+                raise JpegFormatError("SOS before the frame header")
+            ns = seg[0]
+            if ns < 1 or ns > 3 or len(seg) != 4 + 2 * ns:
+                raise JpegFormatError("malformed SOS")
+            ids = [c["id"] for c in frame["components"]]
+            sc = []
+            for k in range(ns):
+                cid, t = seg[1 + 2 * k:3 + 2 * k]
+                if cid not in ids:
+                    raise JpegFormatError(f"SOS names component {cid} the frame lacks")
+                sc.append(dict(index=ids.index(cid), td=t >> 4, ta=t & 15))
+            ss, se, a = seg[1 + 2 * ns:4 + 2 * ns]
+            if (ss, se, a) != (0, 63, 0):
+                raise JpegFormatError("not supported: spectral selection / successive approximation")
+            if ns > 1 and sum(frame["components"][c["index"]]["h"] * frame["components"][c["index"]]["v"] for c in sc) > 10:
+                raise JpegFormatError("more than 10 blocks per MCU")
+            if dri == 0:
+                raise JpegFormatError("not supported: a scan without restart markers (no DRI or restart interval 0)")
+            end = _entropy_end(data, i)
+            scans.append(dict(components=sc, restart_interval=dri, start=i, end=end, huffman=dict(ht), qtables=dict(qt)))
+            i = end
+        elif 0xE0 <= m <= 0xEF or m == 0xFE:
+            pass  # APPn, COM
+        else:
+            raise JpegFormatError(f"not supported: marker 0x{m:02x}")
+    if frame is None or not scans:
+        raise JpegFormatError("no frame or no scan")
+    return dict(frame, qtables=qt, huffman=ht, scans=scans)

@@ -1,0 +1,178 @@
+"""Restart-marked baseline JPEG -> 8-bit planes on the GPU (libmdct_jpegdec.so, include/mdct_jpegdec.h).
+
+decode_jpeg parses the file on the host (jfif.read_jpeg), uploads each scan, finds its restart intervals (mdct_jpegdec_index),
+decodes them into quantised int16 coefficient planes (mdct_jpegdec_decode), checks every interval's status, and runs
+mdct_inv_i16_u8_batch over the planes with each component's DQT as the table.  One uint8 plane per component, cropped to the
+component's size (T.81 A.1.1); no chroma upsampling and no colour conversion.  torch is used for device memory and streams only.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _jpegdec_lib, api, jfif
+from .api import _ptr, _stream
+
+
+class JpegDecodeError(RuntimeError):
+    """a scan with restart intervals that did not decode cleanly; .status holds the per-interval MDCT_JPEGDEC_* codes of that scan"""
+
+    def __init__(self, msg, scan=None, status=None):
+        super().__init__(msg)
+        self.scan = scan
+        self.status = status
+
+
+def last_error():
+    return _jpegdec_lib.load().mdct_jpegdec_last_error().decode()
+
+
+def _check(rc):
+    if rc != 0:
+        raise api.MdctError(f"mdct_jpegdec status {rc}: {last_error()}")
+
+
+def _spec_arrays(specs):
+    """specs: 4 x (bits16, vals) or None -> the three C arrays of mdct_jpegdec_tables_create (and the buffers they point into)"""
+    keep = []
+    bits_p = (ctypes.c_void_p * 4)()
+    vals_p = (ctypes.c_void_p * 4)()
+    nv = (ctypes.c_int * 4)()
+    for i, sp in enumerate(specs):
+        if sp is None:
+            continue
+        b = np.ascontiguousarray(np.asarray(sp[0], dtype=np.uint8).reshape(16))
+        v = np.ascontiguousarray(np.asarray(sp[1], dtype=np.uint8).reshape(-1)) if len(sp[1]) else np.zeros(1, dtype=np.uint8)
+        keep += [b, v]
+        bits_p[i] = b.ctypes.data
+        vals_p[i] = v.ctypes.data
+        nv[i] = len(sp[1])
+    return bits_p, vals_p, nv, keep
+
+
+def tables_check(specs):
+    """mdct_jpegdec_tables_check (host only): 0 or MDCT_INVALID_PARAMETER"""
+    b, v, n, keep = _spec_arrays(specs)
+    return _jpegdec_lib.load().mdct_jpegdec_tables_check(b, v, n)
+
+
+class Tables:
+    """device-resident Huffman tables (mdct_jpegdec_tables_*): specs = 4 x (bits16, vals) or None -- slots 0, 1 DC; 2, 3 AC"""
+
+    def __init__(self, specs):
+        lib = _jpegdec_lib.load()
+        b, v, n, keep = _spec_arrays(specs)
+        h = ctypes.c_void_p()
+        _check(lib.mdct_jpegdec_tables_create(ctypes.byref(h), b, v, n))
+        self.handle = h
+
+    def close(self):
+        if self.handle:
+            _jpegdec_lib.load().mdct_jpegdec_tables_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def scan_desc(planes, mcus_x, mcus_y, restart_interval):
+    """planes: list of (coef int16 tensor [rows, pitch], blocks_x, blocks_y, h, v, dc_slot, ac_slot) -> mdct_jpegdec_scan"""
+    d = _jpegdec_lib.Scan()
+    d.n_components = len(planes)
+    for c, (t, bx, by, h, v, dc, ac) in enumerate(planes):
+        d.comp[c] = _jpegdec_lib.Component(_ptr(t), t.shape[-1], bx, by, h, v, dc, ac)
+    d.mcus_x, d.mcus_y, d.restart_interval = mcus_x, mcus_y, restart_interval
+    return d
+
+
+def n_intervals(desc):
+    n = int(_jpegdec_lib.load().mdct_jpegdec_intervals(ctypes.byref(desc)))
+    if n == 0:
+        raise api.MdctError(f"invalid scan descriptor: {last_error()}")
+    return n
+
+
+def index(scan, n, offsets, status, scan_len=None, stream=None):
+    """mdct_jpegdec_index: offsets = n + 1 int64 device tensor, status = n int32 device tensor (scratch)"""
+    L = scan.numel() if scan_len is None else scan_len
+    _check(_jpegdec_lib.load().mdct_jpegdec_index(_ptr(scan), L, n, _ptr(offsets), _ptr(status), _stream(stream)))
+
+
+def decode(desc, tables, scan, offsets, status, scan_len=None, stream=None):
+    """mdct_jpegdec_decode"""
+    L = scan.numel() if scan_len is None else scan_len
+    _check(_jpegdec_lib.load().mdct_jpegdec_decode(ctypes.byref(desc), tables.handle, _ptr(scan), L, _ptr(offsets), _ptr(status), _stream(stream)))
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def geometry(info):
+    """per component of read_jpeg's frame: (true width, true height, plane blocks_x, plane blocks_y), planes padded to the MCU grid"""
+    comps = info["components"]
+    hmax, vmax = max(c["h"] for c in comps), max(c["v"] for c in comps)
+    mx, my = _ceil(info["width"], 8 * hmax), _ceil(info["height"], 8 * vmax)
+    return [(_ceil(info["width"] * c["h"], hmax), _ceil(info["height"] * c["v"], vmax), mx * c["h"], my * c["v"]) for c in comps], (mx, my)
+
+
+def scan_geometry(info, scan, geo, grid):
+    """(mcus_x, mcus_y, [(component index, h, v)]) of one scan: T.81 A.2.2 (one component: its own block grid) / A.2.3"""
+    if len(scan["components"]) == 1:
+        ci = scan["components"][0]["index"]
+        w, h = geo[ci][0], geo[ci][1]
+        return _ceil(w, 8), _ceil(h, 8), [(ci, 1, 1)]
+    comps = info["components"]
+    return grid[0], grid[1], [(c["index"], comps[c["index"]]["h"], comps[c["index"]]["v"]) for c in scan["components"]]
+
+
+def decode_jpeg(data, device=None, coefficients=False, stream=None):
+    """Decode a restart-marked baseline JPEG on the GPU.  Returns one uint8 tensor [height, width] per component (cropped to its true
+    size); with coefficients=True also the quantised int16 coefficient planes ([blocks_y * 8, blocks_x * 8], padded to the MCU grid):
+    (planes, coefficient planes).  Raises jfif.JpegFormatError for a file outside the supported subset and JpegDecodeError when a
+    restart interval does not decode cleanly."""
+    import torch
+
+    info = jfif.read_jpeg(data)
+    dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+    raw = bytes(data)
+    geo, grid = geometry(info)
+    coefs = [torch.empty((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
+    with torch.cuda.device(dev):
+        for si, sc in enumerate(info["scans"]):
+            mcus_x, mcus_y, members = scan_geometry(info, sc, geo, grid)
+            specs = [None] * 4
+            planes = []
+            for c, (ci, h, v) in zip(sc["components"], members):
+                for slot, key in ((c["td"], (0, c["td"])), (2 + c["ta"], (1, c["ta"]))):
+                    if key not in sc["huffman"]:
+                        raise jfif.JpegFormatError(f"scan {si} uses Huffman table {key} that is not defined")
+                    specs[slot] = sc["huffman"][key]
+                planes.append((coefs[ci], geo[ci][2], geo[ci][3], h, v, c["td"], 2 + c["ta"]))
+            tables = Tables(specs)
+            desc = scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"])
+            n = n_intervals(desc)
+            seg = torch.frombuffer(bytearray(raw[sc["start"]:sc["end"]]) or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
+            L = sc["end"] - sc["start"]
+            off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+            index(seg, n, off, status, scan_len=L, stream=stream)
+            decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
+            st = status.cpu().numpy()
+            tables.close()
+            bad = np.flatnonzero(st)
+            if bad.size:
+                k = int(bad[0])
+                raise JpegDecodeError(f"scan {si}: {bad.size} of {n} restart intervals failed; interval {k}: "
+                                      f"{_jpegdec_lib.STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
+        px = [torch.empty((by * 8, bx * 8), dtype=torch.uint8, device=dev) for _, _, bx, by in geo]
+        luts = []
+        for c in info["components"]:
+            if c["tq"] not in info["qtables"]:
+                raise jfif.JpegFormatError(f"quantisation table {c['tq']} is not defined")
+            luts.append(info["qtables"][c["tq"]].astype(np.float32))
+        api.u8_i16_batch("inv", [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, lut in zip(px, coefs, geo, luts)], level_shift=True, stream=stream)
+    out = [p[:g[1], :g[0]] for p, g in zip(px, geo)]
+    return (out, coefs) if coefficients else out
