@@ -11,8 +11,9 @@
  * library's last failure is mdct_jpegdec_last_error().  The library links against libmdct_hip.so; its launches appear in
  * mdct_kernel_counts().
  *
- * Out of scope: scans without restart markers (one serial interval), progressive / arithmetic / 12-bit / lossless JPEG, chroma upsampling
- * and colour conversion. */
+ * Scans without restart markers (restart_interval 0, refused here) are decoded by libmdct_jpegdec_unmarked.so
+ * (include/mdct_jpegdec_unmarked.h), with the same table handle and descriptor.
+ * Out of scope: progressive / arithmetic / 12-bit / lossless JPEG, chroma upsampling and colour conversion. */
 #ifndef MDCT_JPEGDEC_H
 #define MDCT_JPEGDEC_H
 

@@ -26,418 +26,13 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "jpegdec_common.h"
 #include "launch_tally.h"
-#include "mdct.h"
-#include "mdct_jpegdec.h"
-#include "wg_sync.h"
-
-namespace
-{
-char g_err[512];
-
-int fail(int code, const char *fmt, ...)
-{
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int hip_fail(hipError_t e, const char *what) { return fail(MDCT_NOT_SUPPORTED, "%s: %s", what, hipGetErrorString(e)); }
-} // namespace
 
 namespace mdct
 {
 namespace jpegdec
 {
-
-constexpr int kThreads = 256;   // lanes per restart interval
-constexpr int kFastBits = 9;    // codes up to 9 bits resolve in one LDS lookup
-constexpr uint32_t kErr = 0x80000000u;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-// T.81 C.2 / F.2.2.3, built on the host: fast[peek9] = (length << 8) | value for codes of <= 9 bits (0: longer code or none);
-// a 16-bit left-justified code c has length l if c < limit[l] (first such l), and its value is vals[(c >> (16 - l)) + delta[l]].
-struct DevTables
-{
-  uint16_t fast[4][1 << kFastBits];
-  int32_t limit[4][18];
-  int32_t delta[4][18];
-  uint8_t vals[4][256];
-};
-static_assert(sizeof(DevTables) % 4 == 0, "LDS copy in words");
-
-struct DecArgs
-{
-  const uint8_t *scan;
-  uint64_t scan_len;
-  const uint64_t *off;
-  uint32_t *status;
-  const DevTables *tab;
-  int16_t *plane[3];
-  uint64_t pitch[3];
-  uint32_t upm;                 // blocks per MCU
-  uint8_t bcomp[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU], bh[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU], bv[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU];
-  uint8_t bdc[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU], bac[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU];
-  uint32_t ch[3], cv[3];        // h, v per component
-  uint32_t mcus_x, total_mcus, restart;
-  uint32_t n_intervals;
-};
-
-__constant__ uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// ------------------------------------------------------------------------------------------------------------------ the bit reader
-struct Reader
-{
-  const uint8_t *scan;
-  uint64_t len;      // the whole scan: no byte outside [scan, scan + len) is read
-  uint64_t p, end;   // next stuffed byte, end of the interval's data
-  uint64_t E;        // first stuffed byte of the next sub-sequence (UINT64_MAX: none)
-  uint64_t buf;      // left-aligned
-  uint32_t nb;       // bits in buf
-  uint32_t u;        // bits consumed since the lane's start (after unstuffing)
-  uint32_t ufill;    // bits appended since the lane's start
-  uint32_t uE;       // ufill when the first data byte at or after E was appended (kNone: not yet)
-  uint32_t uend;     // ufill when the data ran out (kNone: not yet)
-  bool dry, marker;
-  uintptr_t wa;      // address of the cached aligned word
-  uint32_t w;
-};
-
-__device__ __forceinline__ uint32_t byte_at(Reader &r, uint64_t p)
-{
-  const uintptr_t q = (uintptr_t)(r.scan + p);
-  const uintptr_t a = q & ~uintptr_t(3);
-  if (a != r.wa)
-  {
-    if (a < (uintptr_t)r.scan || a + 4 > (uintptr_t)(r.scan + r.len))
-      return r.scan[p]; // a word that would leave the buffer: this byte alone
-    r.w = *(const uint32_t *)a;
-    r.wa = a;
-  }
-  return (r.w >> (8 * (q & 3))) & 0xFFu;
-}
-
-__device__ __forceinline__ void refill(Reader &r)
-{
-  while (r.nb <= 56) // at most 8 rounds
-  {
-    uint32_t b = 0;
-    if (!r.dry)
-    {
-      if (r.p >= r.end)
-      {
-        r.dry = true;
-        r.uend = r.ufill;
-      }
-      else
-      {
-        b = byte_at(r, r.p);
-        uint32_t step = 1;
-        if (b == 0xFF)
-        {
-          const uint32_t b2 = r.p + 1 < r.end ? byte_at(r, r.p + 1) : 0x100u;
-          if (b2 == 0)
-            step = 2;
-          else
-          {
-            r.dry = r.marker = true;
-            r.uend = r.ufill;
-            b = 0;
-          }
-        }
-        if (!r.dry)
-        {
-          if (r.uE == kNone && r.p >= r.E)
-            r.uE = r.ufill;
-          r.p += step;
-        }
-      }
-    }
-    r.buf |= (uint64_t)b << (56 - r.nb);
-    r.nb += 8;
-    r.ufill += 8;
-  }
-}
-
-__device__ __forceinline__ void consume(Reader &r, uint32_t n)
-{
-  r.buf <<= n;
-  r.nb -= n;
-  r.u += n;
-}
-
-__device__ __forceinline__ uint32_t get_bits(Reader &r, uint32_t s)
-{
-  const uint32_t v = s ? (uint32_t)(r.buf >> (64 - s)) : 0u;
-  consume(r, s);
-  return v;
-}
-
-__device__ __forceinline__ int extend(uint32_t v, uint32_t s)
-{
-  return s == 0 ? 0 : ((int)v < (1 << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v);
-}
-
-__device__ __forceinline__ bool overrun(const Reader &r) { return r.dry && r.u > r.uend; }
-
-__device__ __forceinline__ uint32_t data_error(const Reader &r) { return r.marker ? MDCT_JPEGDEC_UNEXPECTED_MARKER : MDCT_JPEGDEC_OUT_OF_DATA; }
-
-// no code matched the next 16 bits: an invalid code if 16 bits of data were there, else the data ran out first
-__device__ __forceinline__ uint32_t no_code(const Reader &r) { return r.dry && r.u + 16 > r.uend ? data_error(r) : MDCT_JPEGDEC_BAD_CODE; }
-
-// one Huffman symbol of table t (LDS); returns -1 for a pattern that is no code
-__device__ __forceinline__ int huff(Reader &r, const DevTables &T, int t)
-{
-  const uint32_t peek = (uint32_t)(r.buf >> 48);
-  const uint32_t f = T.fast[t][peek >> (16 - kFastBits)];
-  if (f)
-  {
-    consume(r, f >> 8);
-    return (int)(f & 0xFF);
-  }
-  for (int l = kFastBits + 1; l <= 16; l++)
-    if ((int32_t)peek < T.limit[t][l])
-    {
-      consume(r, l);
-      return T.vals[t][((peek >> (16 - l)) + T.delta[t][l]) & 0xFF];
-    }
-  return -1;
-}
-
-struct Lane
-{
-  uint32_t state;    // packed start / exit state: kErr | d << 12 | k << 4 | b
-  int blocks;        // blocks completed
-  int dc[3];         // sum of the DC differences per component
-  uint32_t err;      // MDCT_JPEGDEC_* of a decode error (final pass)
-  bool finished;     // completed the interval's last block (final pass)
-  uint32_t fin;      // status after the last block: OK / LEFTOVER / UNEXPECTED_MARKER
-};
-
-__device__ __forceinline__ void reader_init(Reader &r, const DecArgs &a, uint64_t s0, uint64_t end, uint64_t E, bool first)
-{
-  r.scan = a.scan;
-  r.len = a.scan_len;
-  r.p = s0;
-  r.end = end;
-  r.E = E;
-  r.buf = 0;
-  r.nb = 0;
-  r.u = r.ufill = 0;
-  r.uE = r.uend = kNone;
-  r.dry = r.marker = false;
-  r.wa = 1;
-  r.w = 0;
-  if (!first && s0 < end && s0 > 0 && byte_at(r, s0 - 1) == 0xFF)
-  {
-    if (byte_at(r, s0) == 0)
-      r.p = s0 + 1; // s0 is the stuffed zero after a data 0xFF
-    else
-    {
-      r.dry = r.marker = true; // s0 is inside a marker
-      r.uend = 0;
-    }
-  }
-}
-
-// Decode from state `start` until the first symbol boundary at or after the next sub-sequence's start (a lane with a successor), the
-// interval's last block (WRITE with a unit budget), or an error.  WRITE: unit0 blocks precede the start; pred = DC predictors there.
-template <bool WRITE>
-__device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint32_t *lcomp, uint32_t start, Lane &out, uint32_t unit0,
-                    uint32_t units, uint32_t mcu0, int pred[3], uint64_t cap)
-{
-  out.blocks = 0;
-  out.dc[0] = out.dc[1] = out.dc[2] = 0;
-  out.err = 0;
-  out.finished = false;
-  out.fin = 0;
-  out.state = kErr;
-  if (start & kErr)
-    return;
-  uint32_t k = (start >> 4) & 0x7F, b = start & 0xF;
-  uint32_t d = start >> 12;
-  for (uint32_t i = 0; i < 64 && d > 0; i++) // skip the bits the previous lane consumed past this sub-sequence's start
-  {
-    refill(r);
-    const uint32_t n = d < 32 ? d : 32;
-    consume(r, n);
-    d -= n;
-  }
-  if (overrun(r))
-  {
-    out.err = data_error(r);
-    return;
-  }
-  uint32_t unit = unit0;
-  if (WRITE && unit >= units)
-    return;
-  // the current block's place (WRITE): MCU (mx, my), block b of it
-  uint32_t mcu = 0, mx = 0, my = 0;
-  int16_t *bp = nullptr;
-  uint32_t comp = lcomp[b];
-  if (WRITE)
-  {
-    mcu = mcu0 + unit / a.upm;
-    my = mcu / a.mcus_x;
-    mx = mcu - my * a.mcus_x;
-    bp = a.plane[comp] + (size_t)(my * a.cv[comp] + a.bv[b]) * 8 * a.pitch[comp] + (size_t)(mx * a.ch[comp] + a.bh[b]) * 8;
-  }
-  for (uint64_t it = 0; it < cap; it++)
-  {
-    refill(r);
-    if (r.uE != kNone && r.u >= r.uE)
-    {
-      out.state = ((r.u - r.uE) << 12) | (k << 4) | b;
-      return;
-    }
-    bool block_end = false;
-    const int sym = huff(r, T, k == 0 ? a.bdc[b] : a.bac[b]);
-    if (sym < 0)
-    {
-      out.err = no_code(r);
-      if (WRITE || out.err != MDCT_JPEGDEC_BAD_CODE)
-        return;
-      consume(r, 1); // speculating: resynchronise instead of stopping (see the kernel's comment)
-      out.err = 0;
-      block_end = true;
-    }
-    else if (k == 0)
-    {
-      const int s = sym;
-      const int diff = extend(get_bits(r, s & 15), s & 15);
-      if (overrun(r))
-      {
-        out.err = data_error(r);
-        return;
-      }
-      out.dc[comp] += diff;
-      if (WRITE)
-      {
-        pred[comp] += diff;
-        bp[0] = (int16_t)pred[comp];
-      }
-      k = 1;
-    }
-    else
-    {
-      const int rs = sym;
-      if (overrun(r))
-      {
-        out.err = data_error(r);
-        return;
-      }
-      const uint32_t run_ = (uint32_t)rs >> 4, s = (uint32_t)rs & 15;
-      if (s == 0)
-      {
-        if (run_ == 15)
-        {
-          k += 16;
-          if (k > 64)
-          {
-            if (WRITE)
-            {
-              out.err = MDCT_JPEGDEC_COEF_OVERFLOW;
-              return;
-            }
-            k = 64; // speculating: end the block
-          }
-          block_end = k == 64;
-        }
-        else
-          block_end = true; // EOB
-      }
-      else
-      {
-        k += run_;
-        if (k > 63)
-        {
-          if (WRITE)
-          {
-            out.err = MDCT_JPEGDEC_COEF_OVERFLOW;
-            return;
-          }
-          k = 63; // speculating: keep the bit position, end the block after this level
-        }
-        const int v = extend(get_bits(r, s), s);
-        if (overrun(r))
-        {
-          out.err = data_error(r);
-          return;
-        }
-        if (WRITE)
-        {
-          const uint32_t z = kZigzag[k];
-          bp[(size_t)(z >> 3) * a.pitch[comp] + (z & 7)] = (int16_t)v;
-        }
-        k++;
-        block_end = k == 64;
-      }
-    }
-    if (block_end)
-    {
-      k = 0;
-      out.blocks++;
-      if (++b == a.upm)
-        b = 0;
-      comp = lcomp[b];
-      if (WRITE)
-      {
-        if (++unit == units)
-        {
-          // the interval's last block: what follows must be its padding (1-bits to the byte boundary) and nothing else
-          out.finished = true;
-          refill(r);
-          uint32_t fin = MDCT_JPEGDEC_LEFTOVER;
-          if (r.dry)
-          {
-            const uint32_t rem = r.uend - r.u;
-            if (rem < 8 && (rem == 0 || (uint32_t)(r.buf >> (64 - rem)) == (1u << rem) - 1u))
-              fin = r.marker ? MDCT_JPEGDEC_UNEXPECTED_MARKER : MDCT_JPEGDEC_OK;
-          }
-          out.fin = fin;
-          return;
-        }
-        if (b == 0 && ++mx == a.mcus_x)
-        {
-          mx = 0;
-          my++;
-        }
-        bp = a.plane[comp] + (size_t)(my * a.cv[comp] + a.bv[b]) * 8 * a.pitch[comp] + (size_t)(mx * a.ch[comp] + a.bh[b]) * 8;
-      }
-    }
-  }
-  out.err = MDCT_JPEGDEC_OUT_OF_DATA; // not reached: every symbol consumes a bit and the data ends
-}
-
-__device__ __forceinline__ int wave_incl_scan(int x, int lane)
-{
-  for (int o = 1; o < 64; o <<= 1)
-  {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o)
-      x += y;
-  }
-  return x;
-}
-
-// exclusive prefix of x over the workgroup (kThreads lanes)
-__device__ __forceinline__ int wg_excl_scan(int x, int *wtot)
-{
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int inc = wave_incl_scan(x, lane);
-  if (lane == 63)
-    wtot[w] = inc;
-  wg_sync();
-  int base = 0;
-  for (int j = 0; j < w; j++)
-    base += wtot[j];
-  wg_sync();
-  return base + inc - x;
-}
 
 __global__ void __launch_bounds__(kThreads) k_decode(DecArgs a)
 {
@@ -651,12 +246,6 @@ __global__ void __launch_bounds__(1024) k_rst_scan(IndexArgs a)
 
 using namespace mdct::jpegdec;
 
-struct mdct_jpegdec_tables
-{
-  DevTables *dev;
-  int device;
-  bool present[4];
-};
 
 static int build_tables(const uint8_t *const bits16[4], const uint8_t *const vals[4], const int nvals[4], DevTables *out, bool present[4])
 {
@@ -770,27 +359,9 @@ static int check_desc(const mdct_jpegdec_scan *d, size_t *n_intervals)
     return fail(MDCT_INVALID_PARAMETER, "%d components (1..3)", d->n_components);
   if (d->mcus_x == 0 || d->mcus_y == 0 || d->restart_interval == 0)
     return fail(MDCT_INVALID_PARAMETER, "empty MCU grid or restart interval 0 (scans without restart markers are not supported)");
-  int upm = 0;
-  for (int c = 0; c < d->n_components; c++)
-  {
-    const mdct_jpegdec_component &q = d->comp[c];
-    if (q.h < 1 || q.h > 2 || q.v < 1 || q.v > 2)
-      return fail(MDCT_INVALID_PARAMETER, "component %d: sampling factors %dx%d (1 or 2)", c, q.h, q.v);
-    if (d->n_components == 1 && (q.h != 1 || q.v != 1))
-      return fail(MDCT_INVALID_PARAMETER, "a non-interleaved scan has one block per MCU (h = v = 1)");
-    if (q.dc_slot < 0 || q.dc_slot > 1 || q.ac_slot < 2 || q.ac_slot > 3)
-      return fail(MDCT_INVALID_PARAMETER, "component %d: table slots %d / %d (DC 0..1, AC 2..3)", c, q.dc_slot, q.ac_slot);
-    if (!q.coef || ((uintptr_t)q.coef & 15) || (q.pitch * sizeof(int16_t)) % 16)
-      return fail(MDCT_INVALID_PARAMETER, "component %d: null or unaligned plane / pitch (rows must be 16-byte aligned)", c);
-    if (d->mcus_x * q.h > q.blocks_x || d->mcus_y * q.v > q.blocks_y || q.pitch < q.blocks_x * 8)
-      return fail(MDCT_INVALID_PARAMETER, "component %d: the MCU grid %zux%zu needs %zux%zu blocks, the plane has %zux%zu (pitch %zu)", c, d->mcus_x,
-                  d->mcus_y, d->mcus_x * q.h, d->mcus_y * q.v, q.blocks_x, q.blocks_y, q.pitch);
-    upm += q.h * q.v;
-  }
-  if (upm > MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU)
-    return fail(MDCT_INVALID_PARAMETER, "%d blocks per MCU (at most 10)", upm);
-  if (d->mcus_x > 0xFFFFFFFFull / d->mcus_y || d->mcus_x * d->mcus_y * (size_t)upm >= (1ull << 31))
-    return fail(MDCT_NOT_SUPPORTED, "more than 2^31 blocks in one scan");
+  const int rc = check_components(d);
+  if (rc)
+    return rc;
   *n_intervals = (d->mcus_x * d->mcus_y + d->restart_interval - 1) / d->restart_interval;
   return MDCT_SUCCESS;
 }
@@ -842,30 +413,8 @@ int mdct_jpegdec_decode(const mdct_jpegdec_scan *desc, const mdct_jpegdec_tables
   a.scan_len = scan_len;
   a.off = interval_offsets;
   a.status = interval_status;
-  a.tab = tables->dev;
-  uint32_t b = 0;
-  for (int c = 0; c < desc->n_components; c++)
-  {
-    const mdct_jpegdec_component &q = desc->comp[c];
-    if (!tables->present[q.dc_slot] || !tables->present[q.ac_slot])
-      return fail(MDCT_INVALID_PARAMETER, "component %d uses an empty table slot (%d / %d)", c, q.dc_slot, q.ac_slot);
-    a.plane[c] = q.coef;
-    a.pitch[c] = q.pitch;
-    a.ch[c] = (uint32_t)q.h;
-    a.cv[c] = (uint32_t)q.v;
-    for (int v = 0; v < q.v; v++) // T.81 A.2.3: a component's blocks in the MCU, left to right, top to bottom
-      for (int h = 0; h < q.h; h++, b++)
-      {
-        a.bcomp[b] = (uint8_t)c;
-        a.bh[b] = (uint8_t)h;
-        a.bv[b] = (uint8_t)v;
-        a.bdc[b] = (uint8_t)q.dc_slot;
-        a.bac[b] = (uint8_t)q.ac_slot;
-      }
-  }
-  a.upm = b;
-  a.mcus_x = (uint32_t)desc->mcus_x;
-  a.total_mcus = (uint32_t)(desc->mcus_x * desc->mcus_y);
+  if ((rc = fill_geometry(desc, tables, a)))
+    return rc;
   a.restart = (uint32_t)(desc->restart_interval < a.total_mcus ? desc->restart_interval : a.total_mcus);
   a.n_intervals = (uint32_t)n;
   MDCT_LAUNCH(k_decode, dim3((uint32_t)n), dim3(kThreads), 0, (hipStream_t)stream, a);

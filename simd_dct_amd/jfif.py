@@ -104,8 +104,9 @@ def _entropy_end(data, i):
             return k
 
 
-def read_jpeg(data):
-    """Parse a baseline (SOF0) or 8-bit extended-sequential Huffman (SOF1) JPEG with restart markers (ITU-T T.81 B.2).
+def read_jpeg(data, require_restart=True):
+    """Parse a baseline (SOF0) or 8-bit extended-sequential Huffman (SOF1) JPEG with restart markers (ITU-T T.81 B.2); with
+    require_restart=False also a scan without them (no DRI, or DRI 0), whose restart_interval is then 0.
     Returns a dict:
       width, height, sof (0xC0 / 0xC1),
       components: [{'id', 'h', 'v', 'tq'}] in frame order,
@@ -114,7 +115,7 @@ def read_jpeg(data):
       scans: [{'components': [{'index' (into components), 'td', 'ta'}], 'restart_interval', 'start', 'end' (byte range of the
                entropy-coded data in `data`, stuffed, RSTm included), 'huffman' / 'qtables' (the tables in force at the scan)}]
     Refuses (JpegFormatError) progressive, lossless, hierarchical and arithmetic-coded files, 12-bit samples, 16-bit DQT, DNL,
-    other than 1 or 3 components, and a scan without a restart interval (no DRI, or DRI 0)."""
+    other than 1 or 3 components, and (require_restart=True) a scan without a restart interval (no DRI, or DRI 0)."""
     data = bytes(data)
     if data[:2] != b"\xff\xd8":
         raise JpegFormatError("no SOI")
@@ -208,7 +209,7 @@ def read_jpeg(data):
                 raise JpegFormatError("not supported: spectral selection / successive approximation")
             if ns > 1 and sum(frame["components"][c["index"]]["h"] * frame["components"][c["index"]]["v"] for c in sc) > 10:
                 raise JpegFormatError("more than 10 blocks per MCU")
-            if dri == 0:
+            if dri == 0 and require_restart:
                 raise JpegFormatError("not supported: a scan without restart markers (no DRI or restart interval 0)")
             end = _entropy_end(data, i)
             scans.append(dict(components=sc, restart_interval=dri, start=i, end=end, huffman=dict(ht), qtables=dict(qt)))

@@ -1,7 +1,9 @@
-"""Restart-marked baseline JPEG -> 8-bit planes on the GPU (libmdct_jpegdec.so, include/mdct_jpegdec.h).
+"""Baseline JPEG -> 8-bit planes on the GPU (libmdct_jpegdec.so, include/mdct_jpegdec.h; libmdct_jpegdec_unmarked.so,
+include/mdct_jpegdec_unmarked.h).
 
-decode_jpeg parses the file on the host (jfif.read_jpeg), uploads each scan, finds its restart intervals (mdct_jpegdec_index),
-decodes them into quantised int16 coefficient planes (mdct_jpegdec_decode), checks every interval's status, and runs
+decode_jpeg parses the file on the host (jfif.read_jpeg), uploads each scan and decodes it into quantised int16 coefficient planes:
+a scan with restart markers by finding its restart intervals (mdct_jpegdec_index) and decoding them (mdct_jpegdec_decode), a scan
+without by mdct_jpegdec_decode_unmarked.  It checks every scan's status, and runs
 mdct_inv_i16_u8_batch over the planes with each component's DQT as the table.  One uint8 plane per component, cropped to the
 component's size (T.81 A.1.1); no chroma upsampling and no colour conversion.  torch is used for device memory and streams only.
 """
@@ -9,12 +11,13 @@ import ctypes
 
 import numpy as np
 
-from . import _jpegdec_lib, api, jfif
+from . import _jpegdec_lib, _jpegdec_unmarked_lib, api, jfif
 from .api import _ptr, _stream
 
 
 class JpegDecodeError(RuntimeError):
-    """a scan with restart intervals that did not decode cleanly; .status holds the per-interval MDCT_JPEGDEC_* codes of that scan"""
+    """a scan that did not decode cleanly; .status holds that scan's per-interval MDCT_JPEGDEC_* codes (restart-marked scan) or
+    [code, blocks decoded before the first error] (scan without restart markers)"""
 
     def __init__(self, msg, scan=None, status=None):
         super().__init__(msg)
@@ -106,6 +109,25 @@ def decode(desc, tables, scan, offsets, status, scan_len=None, stream=None):
     _check(_jpegdec_lib.load().mdct_jpegdec_decode(ctypes.byref(desc), tables.handle, _ptr(scan), L, _ptr(offsets), _ptr(status), _stream(stream)))
 
 
+def unmarked_last_error():
+    return _jpegdec_unmarked_lib.load().mdct_jpegdec_unmarked_last_error().decode()
+
+
+def unmarked_workspace(desc, scan_len):
+    """mdct_jpegdec_unmarked_workspace (host only): bytes of device workspace, 0 for a descriptor the unmarked path refuses"""
+    return int(_jpegdec_unmarked_lib.load().mdct_jpegdec_unmarked_workspace(ctypes.byref(desc), scan_len))
+
+
+def decode_unmarked(desc, tables, scan, workspace, status, scan_len=None, sync_rounds=4, stream=None):
+    """mdct_jpegdec_decode_unmarked: workspace = device tensor of at least unmarked_workspace() bytes, status = 2 int32 device tensor"""
+    L = scan.numel() if scan_len is None else scan_len
+    rc = _jpegdec_unmarked_lib.load().mdct_jpegdec_decode_unmarked(ctypes.byref(desc), tables.handle, _ptr(scan), L, _ptr(workspace),
+                                                                   workspace.numel() * workspace.element_size(), _ptr(status),
+                                                                   sync_rounds, _stream(stream))
+    if rc != 0:
+        raise api.MdctError(f"mdct_jpegdec status {rc}: {unmarked_last_error()}")
+
+
 def _ceil(a, b):
     return -(-a // b)
 
@@ -129,13 +151,13 @@ def scan_geometry(info, scan, geo, grid):
 
 
 def decode_jpeg(data, device=None, coefficients=False, stream=None):
-    """Decode a restart-marked baseline JPEG on the GPU.  Returns one uint8 tensor [height, width] per component (cropped to its true
-    size); with coefficients=True also the quantised int16 coefficient planes ([blocks_y * 8, blocks_x * 8], padded to the MCU grid):
-    (planes, coefficient planes).  Raises jfif.JpegFormatError for a file outside the supported subset and JpegDecodeError when a
-    restart interval does not decode cleanly."""
+    """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file).  Returns one uint8
+    tensor [height, width] per component (cropped to its true size); with coefficients=True also the quantised int16 coefficient planes
+    ([blocks_y * 8, blocks_x * 8], padded to the MCU grid): (planes, coefficient planes).  Raises jfif.JpegFormatError for a file
+    outside the supported subset and JpegDecodeError when a scan does not decode cleanly."""
     import torch
 
-    info = jfif.read_jpeg(data)
+    info = jfif.read_jpeg(data, require_restart=False)
     dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
     raw = bytes(data)
     geo, grid = geometry(info)
@@ -153,9 +175,16 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None):
                 planes.append((coefs[ci], geo[ci][2], geo[ci][3], h, v, c["td"], 2 + c["ta"]))
             tables = Tables(specs)
             desc = scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"])
-            n = n_intervals(desc)
             seg = torch.frombuffer(bytearray(raw[sc["start"]:sc["end"]]) or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
             L = sc["end"] - sc["start"]
+            if sc["restart_interval"] == 0:
+                st = _decode_unmarked_scan(torch, desc, tables, seg, L, dev, stream)
+                tables.close()
+                if st[0] != 0:
+                    raise JpegDecodeError(f"scan {si} (no restart markers): {_jpegdec_unmarked_lib.STATUS_NAMES.get(int(st[0]), int(st[0]))} "
+                                          f"after {int(st[1])} blocks", scan=si, status=st)
+                continue
+            n = n_intervals(desc)
             off = torch.empty(n + 1, dtype=torch.int64, device=dev)
             status = torch.empty(n, dtype=torch.int32, device=dev)
             index(seg, n, off, status, scan_len=L, stream=stream)
@@ -176,3 +205,20 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None):
         api.u8_i16_batch("inv", [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, lut in zip(px, coefs, geo, luts)], level_shift=True, stream=stream)
     out = [p[:g[1], :g[0]] for p, g in zip(px, geo)]
     return (out, coefs) if coefficients else out
+
+
+def _decode_unmarked_scan(torch, desc, tables, seg, L, dev, stream):
+    """one scan without restart markers -> its status [code, blocks]; a NOT_SYNCHRONISED result (an ordinary status, not a fault) is
+    decoded once more with one fix round per chunk, which always converges"""
+    nbytes = unmarked_workspace(desc, L)
+    if nbytes == 0:
+        raise api.MdctError(f"invalid scan descriptor: {unmarked_last_error()}")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # the caching allocator's blocks are 512-byte aligned
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    decode_unmarked(desc, tables, seg, work, status, scan_len=L, stream=stream)
+    st = status.cpu().numpy()
+    if st[0] == _jpegdec_unmarked_lib.NOT_SYNCHRONISED:
+        rounds = max(1, _ceil(L, _jpegdec_unmarked_lib.CHUNK_BYTES))
+        decode_unmarked(desc, tables, seg, work, status, scan_len=L, sync_rounds=rounds, stream=stream)
+        st = status.cpu().numpy()
+    return st
