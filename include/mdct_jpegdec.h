@@ -52,7 +52,8 @@ int mdct_jpegdec_tables_check(const uint8_t *const bits16[4], const uint8_t *con
 /* Where the restart intervals are: scan = device pointer to the entropy-coded bytes between the SOS header and EOI, still stuffed and with
  * their RSTm markers.  On completion interval_offsets[0] = 0, interval_offsets[j + 1] = the offset just after the j-th RSTm marker
  * (j < n_intervals - 1) and interval_offsets[n_intervals] = scan_len; an interval whose marker is missing gets scan_len + 2 (no data, no
- * marker).  Interval k's data is [interval_offsets[k], interval_offsets[k + 1] - 2) and the last one's [.., scan_len).  Surplus markers
+ * marker).  Interval k's data is [interval_offsets[k], interval_offsets[k + 1] - 2) and the last one's [.., scan_len), except that 0xFF
+ * bytes directly before an RSTm are fill bytes (T.81 B.1.1.2) and mdct_jpegdec_decode leaves them out of the interval.  Surplus markers
  * stay inside the last interval (the decoder reports them).  Whether the markers run RST0..RST7 in order is checked by
  * mdct_jpegdec_decode.  interval_status (n_intervals device uint32) is scratch here; mdct_jpegdec_decode writes it.  Three launches. */
 int mdct_jpegdec_index(const uint8_t *scan, size_t scan_len, size_t n_intervals, uint64_t *interval_offsets, uint32_t *interval_status,

@@ -65,6 +65,11 @@ __global__ void __launch_bounds__(kThreads) k_decode(DecArgs a)
   s = s < len ? s : len;
   e = e < len ? e : len;
   e = e > s ? e : s;
+  // T.81 B.1.1.2: 0xFF bytes directly before the interval's RSTm are fill bytes, not data (a data 0xFF is always followed by its
+  // stuffed zero).  The last interval's end is the scan's, which the caller gives without them.
+  if (!last && next <= len)
+    for (uint64_t i = 0, n = e - s; i < n && a.scan[e - 1] == 0xFF; i++)
+      e--;
   const uint64_t nbytes = e - s;
   uint64_t sb = (nbytes + kThreads - 1) / kThreads;
   sb = sb < 8 ? 8 : sb;

@@ -87,7 +87,7 @@ _SOF_REFUSED = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "hier
 
 def _entropy_end(data, i):
     """offset of the first marker after entropy-coded data starting at i that is neither a stuffed 0xFF nor RSTm"""
-    n = len(data)
+    n, i0 = len(data), i
     while True:
         j = data.find(b"\xff", i)
         if j < 0 or j + 1 >= n:
@@ -99,7 +99,7 @@ def _entropy_end(data, i):
             i = j + 1  # fill byte before a marker
         else:
             k = j
-            while k > i and data[k - 1] == 0xFF:  # fill bytes belong to the marker
+            while k > i0 and data[k - 1] == 0xFF:  # fill bytes belong to the marker (a data 0xFF is followed by its stuffed zero)
                 k -= 1
             return k
 

@@ -161,7 +161,9 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None):
     dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
     raw = bytes(data)
     geo, grid = geometry(info)
-    coefs = [torch.empty((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
+    # zeroed: a non-interleaved scan of a subsampled component covers its own block grid (T.81 A.2.2), which may be smaller than the
+    # plane padded to the MCU grid
+    coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
     with torch.cuda.device(dev):
         for si, sc in enumerate(info["scans"]):
             mcus_x, mcus_y, members = scan_geometry(info, sc, geo, grid)

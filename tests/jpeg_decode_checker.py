@@ -56,7 +56,10 @@ def parse(data):
             j = i
             while not (data[j] == 0xFF and data[j + 1] not in (0x00, 0xFF) and not 0xD0 <= data[j + 1] <= 0xD7):
                 j += 1
-            scans.append((comps, dri, i, j, dict(huff)))
+            end = j
+            while end > i and data[end - 1] == 0xFF:  # B.1.1.2: fill bytes before the marker are not data
+                end -= 1
+            scans.append((comps, dri, i, end, dict(huff)))
             i = j
     return frame, qt, scans
 
@@ -75,12 +78,16 @@ def code_table(bits, vals):
 
 def split_intervals(scan, n):
     """the scan's bytes -> n (data bytes, marker number after it or None) in the order of the RSTm markers; surplus markers stay in the
-    last interval's data, missing intervals are (b'', None)"""
+    last interval's data, missing intervals are (b'', None).  0xFF bytes directly before an RSTm are fill bytes (B.1.1.2), not data: a
+    data 0xFF is always followed by its stuffed zero."""
     cuts = [p for p in range(len(scan) - 1) if scan[p] == 0xFF and 0xD0 <= scan[p + 1] <= 0xD7]
     out, s = [], 0
     for j in range(n - 1):
         if j < len(cuts):
-            out.append((scan[s:cuts[j]], scan[cuts[j] + 1] - 0xD0))
+            e = cuts[j]
+            while e > s and scan[e - 1] == 0xFF:
+                e -= 1
+            out.append((scan[s:e], scan[cuts[j] + 1] - 0xD0))
             s = cuts[j] + 2
         else:
             out.append((b"", None) if s > len(scan) else (scan[s:], None))
