@@ -13,7 +13,7 @@
  *
  * Scans without restart markers (restart_interval 0, refused here) are decoded by libmdct_jpegdec_unmarked.so
  * (include/mdct_jpegdec_unmarked.h), with the same table handle and descriptor.
- * Out of scope: progressive / arithmetic / 12-bit / lossless JPEG, chroma upsampling and colour conversion. */
+ * Out of scope: progressive / arithmetic / 12-bit / lossless JPEG.  Chroma upsampling and colour conversion: include/mdct_jpegcolor.h. */
 #ifndef MDCT_JPEGDEC_H
 #define MDCT_JPEGDEC_H
 

@@ -114,6 +114,9 @@ def read_jpeg(data, require_restart=True):
       huffman: {(table_class, th): (bits16 list, vals list)} as last defined (class 0 DC, 1 AC),
       scans: [{'components': [{'index' (into components), 'td', 'ta'}], 'restart_interval', 'start', 'end' (byte range of the
                entropy-coded data in `data`, stuffed, RSTm included), 'huffman' / 'qtables' (the tables in force at the scan)}]
+      colorspace: 'grey' (one component), 'YCbCr' or 'RGB' (three) as libjpeg decides it: a JFIF APP0 means YCbCr, else an Adobe
+               APP14 decides (transform 0: RGB, any other: YCbCr), else component ids 'R', 'G', 'B' mean RGB and any others YCbCr;
+               None for other component counts
     Refuses (JpegFormatError) progressive, lossless, hierarchical and arithmetic-coded files, 12-bit samples, 16-bit DQT, DNL,
     other than 1 or 3 components, and (require_restart=True) a scan without a restart interval (no DRI, or DRI 0)."""
     data = bytes(data)
@@ -122,6 +125,7 @@ def read_jpeg(data, require_restart=True):
     zz = api.zigzag_table()
     i, n = 2, len(data)
     frame, qt, ht, dri, scans = None, {}, {}, 0, []
+    jfif, adobe = False, None  # APP0 'JFIF\0' seen; transform byte of the last APP14 'Adobe'
     while True:
         while i < n and data[i] == 0xFF and i + 1 < n and data[i + 1] == 0xFF:
             i += 1  # fill bytes
@@ -215,9 +219,26 @@ def read_jpeg(data, require_restart=True):
             scans.append(dict(components=sc, restart_interval=dri, start=i, end=end, huffman=dict(ht), qtables=dict(qt)))
             i = end
         elif 0xE0 <= m <= 0xEF or m == 0xFE:
-            pass  # APPn, COM
+            # APPn, COM: only the two that decide the colour space are read, at the lengths libjpeg requires of them
+            if m == 0xE0 and len(seg) >= 14 and seg[:5] == b"JFIF\x00":
+                jfif = True
+            elif m == 0xEE and len(seg) >= 12 and seg[:5] == b"Adobe":
+                adobe = seg[11]
         else:
             raise JpegFormatError(f"not supported: marker 0x{m:02x}")
     if frame is None or not scans:
         raise JpegFormatError("no frame or no scan")
-    return dict(frame, qtables=qt, huffman=ht, scans=scans)
+    return dict(frame, qtables=qt, huffman=ht, scans=scans, colorspace=_colorspace(frame["components"], jfif, adobe))
+
+
+def _colorspace(comps, jfif, adobe):
+    """libjpeg's default_decompress_parms (jdapimin.c) for one and three components"""
+    if len(comps) == 1:
+        return "grey"
+    if len(comps) != 3:
+        return None
+    if jfif:
+        return "YCbCr"
+    if adobe is not None:
+        return "RGB" if adobe == 0 else "YCbCr"
+    return "RGB" if [c["id"] for c in comps] == [ord("R"), ord("G"), ord("B")] else "YCbCr"

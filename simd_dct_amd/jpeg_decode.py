@@ -5,13 +5,15 @@ decode_jpeg parses the file on the host (jfif.read_jpeg), uploads each scan and 
 a scan with restart markers by finding its restart intervals (mdct_jpegdec_index) and decoding them (mdct_jpegdec_decode), a scan
 without by mdct_jpegdec_decode_unmarked.  It checks every scan's status, and runs
 mdct_inv_i16_u8_batch over the planes with each component's DQT as the table.  One uint8 plane per component, cropped to the
-component's size (T.81 A.1.1); no chroma upsampling and no colour conversion.  torch is used for device memory and streams only.
+component's size (T.81 A.1.1).  With mode="RGB" the planes go through one more launch, mdct_jpegcolor_to_rgb
+(libmdct_jpegcolor.so, include/mdct_jpegcolor.h): chroma upsampling and YCbCr -> RGB as libjpeg-turbo's default decode gives them.
+torch is used for device memory and streams only.
 """
 import ctypes
 
 import numpy as np
 
-from . import _jpegdec_lib, _jpegdec_unmarked_lib, api, jfif
+from . import _jpegcolor_lib, _jpegdec_lib, _jpegdec_unmarked_lib, api, jfif
 from .api import _ptr, _stream
 
 
@@ -150,14 +152,22 @@ def scan_geometry(info, scan, geo, grid):
     return grid[0], grid[1], [(c["index"], comps[c["index"]]["h"], comps[c["index"]]["v"]) for c in scan["components"]]
 
 
-def decode_jpeg(data, device=None, coefficients=False, stream=None):
+def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None, layout="HWC"):
     """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file).  Returns one uint8
     tensor [height, width] per component (cropped to its true size); with coefficients=True also the quantised int16 coefficient planes
-    ([blocks_y * 8, blocks_x * 8], padded to the MCU grid): (planes, coefficient planes).  Raises jfif.JpegFormatError for a file
-    outside the supported subset and JpegDecodeError when a scan does not decode cleanly."""
+    ([blocks_y * 8, blocks_x * 8], padded to the MCU grid): (planes, coefficient planes).
+    mode="RGB" returns one uint8 image instead of the planes, [height, width, 3] (layout="HWC") or [3, height, width] (layout="CHW"),
+    upsampled and converted as libjpeg-turbo's default decode does it (to_rgb); with coefficients=True: (image, coefficient planes).
+    Raises jfif.JpegFormatError for a file outside the supported subset and JpegDecodeError when a scan does not decode cleanly."""
     import torch
 
+    if mode not in (None, "RGB"):
+        raise ValueError(f"mode {mode!r} (None or 'RGB')")
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r} ('HWC' or 'CHW')")
     info = jfif.read_jpeg(data, require_restart=False)
+    if mode == "RGB":
+        _colour_params(info)
     dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
     raw = bytes(data)
     geo, grid = geometry(info)
@@ -205,8 +215,59 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None):
                 raise jfif.JpegFormatError(f"quantisation table {c['tq']} is not defined")
             luts.append(info["qtables"][c["tq"]].astype(np.float32))
         api.u8_i16_batch("inv", [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, lut in zip(px, coefs, geo, luts)], level_shift=True, stream=stream)
-    out = [p[:g[1], :g[0]] for p, g in zip(px, geo)]
+        out = [p[:g[1], :g[0]] for p, g in zip(px, geo)]
+        if mode == "RGB":
+            out = to_rgb(out, [(c["h"], c["v"]) for c in info["components"]], info["width"], info["height"], colour=info["colorspace"],
+                         layout=layout, stream=stream)
     return (out, coefs) if coefficients else out
+
+
+_COLOURS = {"YCbCr": _jpegcolor_lib.YCBCR, "RGB": _jpegcolor_lib.RGB, "grey": _jpegcolor_lib.GREY}
+_LAYOUTS = {"HWC": _jpegcolor_lib.HWC, "CHW": _jpegcolor_lib.CHW}
+
+
+def _colour_params(info):
+    """refuse (JpegFormatError) a file the colour stage does not take: other than 1 or 3 components, a fractional sampling ratio"""
+    comps = info["components"]
+    if info.get("colorspace") not in _COLOURS:
+        raise jfif.JpegFormatError(f"no RGB conversion for {len(comps)} components")
+    hmax, vmax = max(c["h"] for c in comps), max(c["v"] for c in comps)
+    if any(hmax % c["h"] or vmax % c["v"] for c in comps):
+        raise jfif.JpegFormatError("fractional sampling ratio: " + ", ".join(f"{c['h']}x{c['v']}" for c in comps))
+
+
+def colour_last_error():
+    return _jpegcolor_lib.load().mdct_jpegcolor_last_error().decode()
+
+
+def to_rgb(planes, sampling, width, height, colour="YCbCr", layout="HWC", out=None, stream=None):
+    """mdct_jpegcolor_to_rgb on device tensors.  planes: one (grey) or three uint8 [rows, columns] components at their true sizes
+    (ceil(width * h / hmax) x ceil(height * v / vmax)); rows may lie any pitch apart, columns must be contiguous.  sampling: [(h, v)]
+    of the frame.  colour: 'YCbCr', 'RGB' (planes R, G, B, not converted) or 'grey'.  out: uint8 [height, width, 3] (HWC) or
+    [3, height, width] (CHW), allocated if None; its rows and planes may lie any pitch apart, its innermost dimension must be contiguous.
+    Returns out."""
+    import torch
+
+    if colour not in _COLOURS or layout not in _LAYOUTS:
+        raise ValueError(f"colour {colour!r} / layout {layout!r}")
+    if len(planes) != len(sampling):
+        raise ValueError(f"{len(planes)} planes, {len(sampling)} sampling factors")
+    arr = (_jpegcolor_lib.Plane * max(1, len(planes)))()
+    for k, (p, (h, v)) in enumerate(zip(planes, sampling)):
+        if p.dtype != torch.uint8 or p.dim() != 2 or p.stride(1) != 1:
+            raise ValueError(f"plane {k}: uint8 [rows, columns] with contiguous columns")
+        arr[k] = _jpegcolor_lib.Plane(p.data_ptr(), p.stride(0), p.shape[1], p.shape[0], h, v)
+    shape = (height, width, 3) if layout == "HWC" else (3, height, width)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=planes[0].device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape or out.stride(-1) != 1 or (layout == "HWC" and out.stride(1) != 3):
+        raise ValueError(f"out: uint8 {list(shape)} with contiguous {'pixels' if layout == 'HWC' else 'rows'}")
+    pitch, stride = (out.stride(0), 0) if layout == "HWC" else (out.stride(1), out.stride(0))
+    rc = _jpegcolor_lib.load().mdct_jpegcolor_to_rgb(arr, len(planes), width, height, _COLOURS[colour], _LAYOUTS[layout], out.data_ptr(),
+                                                     pitch, stride, _stream(stream))
+    if rc != 0:
+        raise api.MdctError(f"mdct_jpegcolor status {rc}: {colour_last_error()}")
+    return out
 
 
 def _decode_unmarked_scan(torch, desc, tables, seg, L, dev, stream):
