@@ -1,0 +1,52 @@
+"""ctypes binding of libmdct_jpegenc.so -- the C-ABI declared in include/mdct_jpegenc.h (RGB -> YCbCr, chroma downsampling and block
+padding of an image before a JPEG encode, on the GPU).
+
+Its own signature table: a separate library, linked against libmdct_hip.so.  No fallback: if the shared object is missing or fails to
+load, every entry point raises.
+"""
+import ctypes
+import os
+
+from . import _lib
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libmdct_jpegenc.so")
+
+c_size_t = ctypes.c_size_t
+c_void_p = ctypes.c_void_p
+c_int = ctypes.c_int
+
+RGB, GREY = 0, 1
+HWC, CHW = 0, 1
+
+
+class Plane(ctypes.Structure):
+    """mdct_jpegenc_plane"""
+
+    _fields_ = [("px", c_void_p), ("pitch", c_size_t), ("width", c_size_t), ("height", c_size_t), ("h", c_int), ("v", c_int)]
+
+
+# name -> (restype, argtypes); every function include/mdct_jpegenc.h declares
+SIGNATURES = {
+    "mdct_jpegenc_from_rgb": (c_int, [c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_int, c_int, ctypes.POINTER(Plane), c_int, c_void_p]),
+    "mdct_jpegenc_last_error": (ctypes.c_char_p, []),
+}
+
+_lib_handle = None
+
+
+def load():
+    """Load libmdct_jpegenc.so (once), after libmdct_hip.so (whose launch tally and HIP runtime it shares)."""
+    global _lib_handle
+    if _lib_handle is not None:
+        return _lib_handle
+    _lib.load()
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
+    lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib_handle = lib
+    return lib

@@ -42,12 +42,15 @@ def scan_bytes(segments, seg_bytes, seg_stride):
     return b"".join(out)
 
 
-def write_jpeg(components, width, height, specs=None):
+def write_jpeg(components, width, height, specs=None, sampling=None):
     """components: list of 1 (grey) or 3 (Y, Cb, Cr with Cb/Cr at half resolution) dicts with keys
          'blocks_per_row', 'qtable' (64 integers 1..255, natural order v*8+u) and either
          'scan' (bytes / uint8 array: the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it) or
          'segments' (uint8 array / bytes), 'seg_bytes' (per block row), 'seg_stride' (stuffed and joined here)
+       width, height: the image size the frame header states; each component's scan covers its own block grid, ceil(true size / 8)
+         blocks per side of the component's true size ceil(width * h / hmax) x ceil(height * v / vmax) (T.81 A.2.2)
        specs: {which: (bits16, vals)} Huffman specifications (default: the library's, api.huffman_spec)
+       sampling: [(h, v)] per component (default: (2, 2), (1, 1), (1, 1) for three components, (1, 1) for one)
        Returns the file as bytes."""
     specs = specs or {w: api.huffman_spec(w) for w in range(4)}
     zz = api.zigzag_table()
@@ -60,10 +63,11 @@ def write_jpeg(components, width, height, specs=None):
         assert np.all(q == np.rint(q)) and q.min() >= 1 and q.max() <= 255, "baseline DQT holds 8-bit integers"
         f.append(_seg(0xDB, bytes([tq]) + bytes(int(q[zz[k]]) for k in range(64))))
     sof = struct.pack(">BHHB", 8, height, width, nc)
-    if nc == 1:
-        sof += bytes([1, 0x11, 0])
-    else:
-        sof += bytes([1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1])
+    if sampling is None:
+        sampling = [(1, 1)] if nc == 1 else [(2, 2), (1, 1), (1, 1)]
+    assert len(sampling) == nc and all(1 <= h <= 4 and 1 <= v <= 4 for h, v in sampling), "sampling factors 1..4 per component"
+    for ci, (h, v) in enumerate(sampling):
+        sof += bytes([ci + 1, (h << 4) | v, min(ci, 1)])
     f.append(_seg(0xC0, sof))
     f.append(_seg(0xC4, _dht(0, 0, *specs[0]) + _dht(1, 0, *specs[1]) + (_dht(0, 1, *specs[2]) + _dht(1, 1, *specs[3]) if nc == 3 else b"")))
     for ci, c in enumerate(components):

@@ -1,0 +1,158 @@
+"""Times the encoder's front stage (libmdct_jpegenc.so, mdct_jpegenc_from_rgb) on full frames, next to mdct_split420_u8_planes on the
+same frame in the same process (it moves the same 4.5 B per pixel at 4:2:0), and encode_jpeg of an 8192x8192 RGB image at q75 4:2:0
+in both scan forms (the fused coder + counted packing, the default, or one launch per component), with the wall clock to the returned bytes split
+into device work, the length readback and the copy of the scans, next to Pillow's encode of the same image on one host core.
+
+Each case runs in a child process of its own under `timeout`; the parent prints one JSON line per case.  Front-stage times are
+HIP-event medians of 5 repetitions of 20 back-to-back launches, per launch; encode times are medians of 5 calls.  Kernel times come
+from a separate `rocprofv3 --kernel-trace --stats` run of the same command.
+
+    python tools/time_jpeg_encode.py [--out FILE]      all cases
+    python tools/time_jpeg_encode.py --case NAME        one case, in this process
+"""
+import argparse
+import io
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+# name -> (W, H, subsampling, layout)
+FRONT_CASES = {
+    "front-8192-420-hwc": (8192, 8192, "4:2:0", "HWC"),
+    "front-8192-420-chw": (8192, 8192, "4:2:0", "CHW"),
+    "front-7680x4320-420-hwc": (7680, 4320, "4:2:0", "HWC"),
+    "front-7680x4320-444-hwc": (7680, 4320, "4:4:4", "HWC"),
+}
+CASES = list(FRONT_CASES) + ["encode-8192-420-q75"]
+REPS, LAUNCHES = 5, 20
+
+
+def _median_us(torch, fn, launches):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(REPS):
+        start.record()
+        for _ in range(launches):
+            fn()
+        end.record()
+        end.synchronize()
+        t.append(start.elapsed_time(end) * 1000.0 / launches)
+    return sorted(t)[len(t) // 2], t
+
+
+def front_case(name):
+    import torch
+
+    from simd_dct_amd import api
+    from simd_dct_amd import jpeg_encode as J
+
+    W, H, sub, layout = FRONT_CASES[name]
+    api.init(0)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    img = torch.randint(0, 256, (H, W, 3) if layout == "HWC" else (3, H, W), dtype=torch.uint8, device="cuda", generator=g)
+    sizes = J.component_sizes(W, H, J.sampling_of(sub))
+    planes = [torch.empty((ph, pw), dtype=torch.uint8, device="cuda") for _, _, pw, ph in sizes]
+    api.kernel_counts_reset()
+    us, reps = _median_us(torch, lambda: J.to_planes(img, sub, layout, planes=planes), LAUNCHES)
+    ran = sorted(k for k in api.kernel_counts() if k.startswith("k_rgb_ycc"))
+    moved = 3 * W * H + sum(pw * ph for _, _, pw, ph in sizes)
+    res = dict(case=name, width=W, height=H, subsampling=sub, layout=layout, kernels=ran, us=round(us, 2), reps_us=[round(x, 2) for x in reps],
+               bytes=moved, tb_s=round(moved / us / 1e6, 3))
+    if sub == "4:2:0":
+        ycc = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device="cuda", generator=g)
+        y, cb, cr = planes
+        sus, sreps = _median_us(torch, lambda: api.split420_u8_planes(ycc, W, H, y, cb, cr), LAUNCHES)
+        res.update(split420_us=round(sus, 2), split420_reps_us=[round(x, 2) for x in sreps], ratio_to_split420=round(us / sus, 3))
+    return res
+
+
+def encode_case(name):
+    import numpy as np
+    import torch
+    from PIL import Image
+
+    from simd_dct_amd import api, synth
+    from simd_dct_amd import jpeg_encode as J
+
+    api.init(0)
+    W, H = 8192, 8192
+    host = np.stack([synth.plane_u8_np(W, H, "photo", seed=31 + k) for k in range(3)], axis=-1)
+    img = torch.from_numpy(host).cuda()
+    res = dict(case=name, width=W, height=H)
+    for form, two in (("one_launch", False), ("two_launch", True)):
+        data = J.encode_jpeg(img, quality=75, two_launch=two)  # warm: allocations, tables
+        wall = []
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            data = J.encode_jpeg(img, quality=75, two_launch=two)
+            wall.append((time.perf_counter() - t0) * 1e6)
+        # the device part alone: the same launches into buffers kept across calls, timed by events
+        sizes = J.component_sizes(W, H, J.sampling_of("4:2:0"))
+        planes = J.to_planes(img, "4:2:0", "HWC")
+        scans = [J._Scan(torch, img.device, pw, ph, pw * ph + 4096) for _, _, pw, ph in sizes]
+        luma, chroma = J.quality_tables(75)
+
+        def device():
+            J.to_planes(img, "4:2:0", "HWC", planes=planes)
+            for k, (p, (_, _, pw, ph), sc) in enumerate(zip(planes, sizes, scans)):
+                J._run_scan(p, pw, ph, luma if k == 0 else chroma, k > 0, sc, two, None)
+
+        dev_us, dev_reps = _median_us(torch, device, 1)
+        device()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ends = torch.stack([sc.off[-1] for sc in scans]).cpu().tolist()
+        t1 = time.perf_counter()
+        parts = [sc.out[:n].cpu().numpy() for sc, n in zip(scans, ends)]
+        t2 = time.perf_counter()
+        res[form] = dict(wall_us=round(sorted(wall)[len(wall) // 2], 1), wall_reps_us=[round(x, 1) for x in wall], device_us=round(dev_us, 1),
+                         device_reps_us=[round(x, 1) for x in dev_reps], length_readback_us=round((t1 - t0) * 1e6, 1),
+                         scan_copy_us=round((t2 - t1) * 1e6, 1), scan_bytes=int(sum(ends)), file_bytes=len(data))
+        del scans, planes, parts
+    t = []
+    for _ in range(3):
+        b = io.BytesIO()
+        t0 = time.process_time()
+        Image.fromarray(host).save(b, "JPEG", quality=75, subsampling=2)
+        t.append((time.process_time() - t0) * 1e6)
+    res.update(pillow_cpu_us=round(sorted(t)[1], 1), pillow_file_bytes=len(b.getvalue()))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", choices=CASES)
+    ap.add_argument("--out")
+    ap.add_argument("--timeout", type=int, default=300)
+    a = ap.parse_args()
+    if a.case:
+        res = encode_case(a.case) if a.case.startswith("encode") else front_case(a.case)
+        print(json.dumps(res), flush=True)
+        return 0
+    lines, rc = [], 0
+    for name in CASES:
+        p = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--case", name],
+                           capture_output=True, text=True)
+        if p.returncode != 0:
+            print(json.dumps(dict(case=name, returncode=p.returncode, stderr=p.stderr[-2000:])), flush=True)
+            rc = p.returncode
+            break  # a failed or faulted child ends the run: nothing more is started on the device
+        line = p.stdout.strip().splitlines()[-1]
+        print(line, flush=True)
+        lines.append(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())
