@@ -219,19 +219,21 @@ ANNEX_K = {
 }
 
 
-def encode_file(frame, scans, planes, specs, qtables=None):
+def encode_file(frame, scans, planes, specs, qtables=None, table_per_component=False):
     """-> (a complete JFIF file, [stats of each scan, with 'start': the scan's first byte in the file]).  qtables: [64] natural order per
-    component (default: 1 for the first component, 2 for the others); components take quantisation table 0 (first) / 1 (others)."""
+    component (default: 1 for the first component, 2 for the others); components take quantisation table 0 (first) / 1 (others), or
+    with table_per_component table ci each (up to 4 components, T.81 B.2.4.1)."""
     nc = len(frame["comps"])
     if qtables is None:
         qtables = [np.ones(64, dtype=np.uint16)] + [np.full(64, 2, dtype=np.uint16)] * (nc - 1)
+    tq_of = list(range(nc)) if table_per_component else [min(ci, 1) for ci in range(nc)]
     f = [b"\xff\xd8", _seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
-    for tq in range(min(nc, 2)):
+    for tq in range(max(tq_of) + 1):
         q = np.asarray(qtables[tq]).reshape(64)
         f.append(_seg(0xDB, bytes([tq]) + bytes(int(q[ZZ[k]]) for k in range(64))))
     sof = struct.pack(">BHHB", 8, frame["height"], frame["width"], nc)
     for ci, (h, v) in enumerate(frame["comps"]):
-        sof += bytes([ci + 1, (h << 4) | v, min(ci, 1)])
+        sof += bytes([ci + 1, (h << 4) | v, tq_of[ci]])
     f.append(_seg(0xC0, sof))
     f.append(_seg(0xC4, b"".join(bytes([(tc << 4) | th]) + bytes(b) + bytes(v) for (tc, th), (b, v) in sorted(specs.items()))))
     stats, dri = [], None

@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import idct_reference as R
 import oracle as O
 import simd_dct_amd as M
 from simd_dct_amd import api, synth
@@ -145,6 +146,16 @@ def check_f32_vs_double(src, got, W, H):
     assert rel.max() < 1e-5, float(rel.max())
 
 
+def check_inv_vs_double(kind, src, got, W, H, lut, by0=0, by1=None, level_shift=True):
+    """an inverse or round trip against the float64 IDCT (tests/idct_reference.py) on the block rows computed: kind 'inv_i16' / 'inv_u8' /
+    'rt_i16' / 'rt_u8' equal to the exact rule wherever the tie window decides the output, 'f32' within the window.  A round trip's
+    block whose forward value sits within the forward window of a .5 tie is left out (full-scale int16 samples under a table of 8 leave
+    out most blocks: tests/test_idct_accuracy.py holds the round trips to the rule on inputs where few are)"""
+    by1 = H // 8 if by1 is None else by1
+    rows = slice(by0 * 8, by1 * 8)
+    R.check_planes(kind, [np.asarray(src)[rows]], [np.asarray(got)[rows]], [lut], level_shift=level_shift, max_skip=1.0)
+
+
 def dev(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
@@ -224,6 +235,8 @@ def _i16_native(mode, W, H, lut, by0, by1, src_kind):
             assert np.array_equal(got, want), int((got != want).sum())
             if mode == 0:
                 check_i16_fwd_vs_double(src, got, W, H, lut, by0, by1)
+            else:
+                check_inv_vs_double("inv_i16" if mode == 1 else "rt_i16", src, got, W, H, lut, by0, by1)
         return check
     return run
 
@@ -275,6 +288,8 @@ def _i16_batch(mode, planes_spec):
                 assert np.array_equal(got, O.i16(I16_MODE[mode], src, W, H, lut=lut)), (W, H)
                 if mode == 0:
                     check_i16_fwd_vs_double(src, got, W, H, lut)
+                else:
+                    check_inv_vs_double("inv_i16" if mode == 1 else "rt_i16", src, got, W, H, lut)
         return check
     return run
 
@@ -335,6 +350,8 @@ def _u8_batch(mode, shapes, lut):
                 assert np.array_equal(got, want), (W, H, int((got != want).sum()))
                 if mode == 1:
                     check_i16_fwd_vs_double(src, got, W, H, lut, u8_shift=128)
+                else:
+                    check_inv_vs_double("inv_u8" if mode == 2 else "rt_u8", src, got, W, H, lut)
         return check
     return run
 
@@ -389,6 +406,8 @@ def _f32(mode, W, H, by0, by1):
             assert np.array_equal(got, want)
             if mode == 0:
                 check_f32_vs_double(src[by0 * 8:by1 * 8], got[by0 * 8:by1 * 8], W, (by1 - by0) * 8)
+            else:
+                check_inv_vs_double("f32", src, got, W, H, None, by0, by1)
         return check
     return run
 
@@ -414,6 +433,8 @@ def _f32_wide(mode):
             assert same, "a period of the output differs from the first"
             if mode == 0:
                 check_f32_vs_double(src, got, W, period)
+            else:
+                check_inv_vs_double("f32", src, got, W, period, None)
         return check
     return run
 
