@@ -1,0 +1,50 @@
+"""ctypes binding of libmdct_jpegenc_scan.so -- the C-ABI declared in include/mdct_jpegenc_scan.h (the three planes of a colour JPEG
+encode -> the Huffman segments of one interleaved scan, on the GPU).
+
+Its own signature table: a separate library, linked against libmdct_hip.so.  No fallback: if the shared object is missing or fails to
+load, every entry point raises.
+"""
+import ctypes
+import os
+
+from . import _lib
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libmdct_jpegenc_scan.so")
+
+c_size_t = ctypes.c_size_t
+c_void_p = ctypes.c_void_p
+c_int = ctypes.c_int
+
+
+class Plane(ctypes.Structure):
+    """mdct_jpegenc_scan_plane"""
+
+    _fields_ = [("px", c_void_p), ("pitch", c_size_t), ("width", c_size_t), ("height", c_size_t), ("h", c_int), ("v", c_int)]
+
+
+# name -> (restype, argtypes); every function include/mdct_jpegenc_scan.h declares
+SIGNATURES = {
+    "mdct_jpegenc_scan_rows": (c_int, [ctypes.POINTER(Plane), c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "mdct_jpegenc_scan_seg_stride": (c_size_t, [c_size_t, c_int]),
+    "mdct_jpegenc_scan_last_error": (ctypes.c_char_p, []),
+}
+
+_lib_handle = None
+
+
+def load():
+    """Load libmdct_jpegenc_scan.so (once), after libmdct_hip.so (whose launch tally, Huffman specifications and HIP runtime it shares)."""
+    global _lib_handle
+    if _lib_handle is not None:
+        return _lib_handle
+    _lib.load()
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
+    lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib_handle = lib
+    return lib

@@ -450,4 +450,147 @@ struct HuffRowCoder16
   }
 };
 
+// ---------------------------------------------------------------------------------------
+// The sibling of HuffRowCoder16 for INTERLEAVED scans (jpeg_encode_scan.hip): lane = the s-th block of the chunk IN SCAN ORDER
+// (T.81 A.2.3), whichever lane transformed it.  The blocks of a chunk were all transformed before the chunk is coded, so a block's DC
+// predictor -- the previous block of the same component -- is an input (the caller reads it from LDS), and so is the lane's table
+// pair (luma or chroma).  No DC exchange between lanes or waves: what remains is the counting walk, the scan of the bit counts, the
+// window loop over the ring with its barriers, the 0xFF count and finish, as above.
+// ---------------------------------------------------------------------------------------
+template <int WAVES, uint32_t RING>
+struct HuffSeqCoder16
+{
+  uint32_t *ring;         // [RING], zeroed
+  uint32_t (*tot)[WAVES]; // [2][WAVES]
+  uint32_t *out_w;        // the segment
+  uint32_t base_bits = 0;
+  uint32_t par = 0;
+  uint32_t ff = 0; // 0xFF bytes among the words this thread has flushed
+
+  // the lane's block: n AC entries in rec[], DC value and predictor, EOB needed unless position 63 is coded; ac / dc: the LDS copies of
+  // the block's tables (size << 16 | code).  Every thread of the workgroup calls; rec and the predictor were written before a barrier.
+  __device__ __forceinline__ void chunk(const uint16_t *rec, int n, bool live, int my_dc, int pred_dc, bool need_eob, const uint32_t *ac, const uint32_t *dc)
+  {
+    constexpr uint32_t kChunk = 64 * WAVES;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t *rec2 = reinterpret_cast<const uint32_t *>(rec); // two entries per LDS read
+    if (!live)
+    {
+      my_dc = pred_dc = 0;
+      n = 0;
+    }
+    const HuffTok dct = huff_dc_token(my_dc - pred_dc, dc);
+    const uint32_t eob = ac[0x00];
+    uint32_t bits = 0;
+    if (live)
+    {
+      bits = dct.len;
+      for (int i = 0; i < n; i += 2)
+      {
+        const uint32_t w = rec2[i >> 1];
+        bits += huff_ac_token12(w & 0xFFFFu, ac).len;
+        if (i + 1 < n)
+          bits += huff_ac_token12(w >> 16, ac).len;
+      }
+      if (need_eob)
+        bits += eob >> 16;
+    }
+    uint32_t incl = bits;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+    {
+      const uint32_t v = __shfl_up(incl, d, 64);
+      if (lane >= (uint32_t)d)
+        incl += v;
+    }
+    if (lane == 63)
+      tot[par][wave] = incl;
+    wg_sync(); // also: every wave has flushed (and cleared) the previous chunk's words
+    uint32_t wave_start = 0, chunk_bits = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < (uint32_t)WAVES; w++)
+    {
+      const uint32_t t = tot[par][w];
+      wave_start += w < wave ? t : 0;
+      chunk_bits += t;
+    }
+    const uint32_t end_bits = base_bits + chunk_bits;
+    const uint32_t w_first = base_bits >> 5, w_end = end_bits >> 5;
+    for (uint32_t win = w_first; win <= w_end; win += RING)
+    {
+      if (win != w_first)
+        wg_sync(); // the previous window's slots are cleared and the clearing ds_writes have landed (HuffRowCoder16, wg_sync.h)
+      if (live)
+      {
+        const uint32_t cur = base_bits + wave_start + (incl - bits);
+        uint32_t widx = cur >> 5;
+        uint32_t acc = 0;
+        uint32_t nacc = cur & 31;
+        auto put = [&](uint32_t tok, uint32_t len) { // 1 <= len <= 27, tok < 2^len
+          const uint32_t total = nacc + len;
+          if (total < 32)
+          {
+            acc = (acc << len) | tok;
+            nacc = total;
+          }
+          else
+          {
+            const uint32_t over = total - 32;
+            if (widx - win < RING)
+              atomicOr(&ring[widx & (RING - 1)], (acc << ((32 - nacc) & 31)) | (tok >> over));
+            widx++;
+            acc = tok & ((1u << over) - 1u);
+            nacc = over;
+          }
+        };
+        put(dct.bits, dct.len);
+        for (int i = 0; i < n; i += 2)
+        {
+          const uint32_t w = rec2[i >> 1];
+          const HuffTok ta = huff_ac_token12(w & 0xFFFFu, ac);
+          put(ta.bits, ta.len);
+          if (i + 1 < n)
+          {
+            const HuffTok tb = huff_ac_token12(w >> 16, ac);
+            put(tb.bits, tb.len);
+          }
+        }
+        if (need_eob)
+          put(eob & 0xFFFFu, eob >> 16);
+        if (nacc && widx - win < RING)
+          atomicOr(&ring[widx & (RING - 1)], acc << (32 - nacc));
+      }
+      wg_sync();
+      const uint32_t stop = min(w_end, win + RING);
+      for (uint32_t w = win + tid; w < stop; w += kChunk)
+      {
+        const uint32_t v = ring[w & (RING - 1)];
+        ff += (uint32_t)__builtin_popcount(ff_bytes(v));
+        out_w[w] = __builtin_bswap32(v);
+        ring[w & (RING - 1)] = 0;
+      }
+    }
+    base_bits = end_bits;
+    par ^= 1;
+  }
+
+  // one thread, after the last chunk (behind a workgroup barrier); *ff_last = 0xFF bytes in the padded last word
+  __device__ __forceinline__ uint32_t finish(uint32_t *ff_last)
+  {
+    const uint32_t rem = base_bits & 31;
+    *ff_last = 0;
+    if (rem)
+    {
+      const uint32_t pad = (8 - (rem & 7)) & 7;
+      uint32_t w = ring[(base_bits >> 5) & (RING - 1)];
+      if (pad)
+        w |= ((1u << pad) - 1u) << (32 - rem - pad);
+      out_w[base_bits >> 5] = __builtin_bswap32(w);
+      const uint32_t nbytes = (rem + 7) / 8; // the stream is MSB first: its bytes are the word's top ones
+      *ff_last = (uint32_t)__builtin_popcount(ff_bytes(w) & (0xFFFFFFFFu << (8 * (4 - nbytes))));
+    }
+    return (base_bits + 7) / 8;
+  }
+};
+
 } // namespace mdct

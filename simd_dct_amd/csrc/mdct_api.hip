@@ -21,6 +21,7 @@
 
 #include "mdct.h"
 #include "mdct_kernels.h"
+#include "own_tables.h"
 
 namespace
 {
@@ -163,57 +164,12 @@ int own_plane_args(const void *from, const void *to, size_t esz, size_t pitch_in
   return MDCT_SUCCESS;
 }
 
-// AAN scale factors a_0 = 1, a_k = sqrt(2) cos(k pi / 16); the 2-D tables are products of
-// doubles rounded once to float (the CPU checker uses the identical expression).
-const double kAanScale[8] = {1.0, 1.387039845322148, 1.306562964876377, 1.175875602419359, 1.0, 0.785694958387102, 0.541196100146197, 0.275899379282943};
-
-void aan_tables_compute(float *fwd, float *inv)
-{
-  for (int v = 0; v < 8; v++)
-    for (int u = 0; u < 8; u++)
-    {
-      const double a = kAanScale[v] * kAanScale[u];
-      fwd[v * 8 + u] = (float)(1.0 / (8.0 * a));
-      inv[v * 8 + u] = (float)(a / 8.0);
-    }
-}
-
-void aan_tables(float *fwd, float *inv)
-{
-  static float s_fwd[64], s_inv[64];
-  static std::once_flag once;
-  std::call_once(once, [] { aan_tables_compute(s_fwd, s_inv); });
-  memcpy(fwd, s_fwd, sizeof(s_fwd));
-  memcpy(inv, s_inv, sizeof(s_inv));
-}
-
-// forward multiplier = (1/lut) * scale, inverse multiplier = lut * scale, each one float op
-// pair_order: the fused round trip runs on packed fp32 and wants both tables in the register-pair order of its
-// column pass, j-major: (j*8 + v)*2 + {0,1} = (v, kAanPairA[j]) / (v, kAanPairB[j])  (mdct_kernels.hip: i16_roundtrip_rows)
+// forward multiplier = (1/lut) * scale, inverse multiplier = lut * scale, each one float op (own_tables.h, shared with the other libraries)
 int make_own_tables(const float *lut, mdct::OwnTables &tb, bool pair_order = false)
 {
-  float ft[64], it[64];
-  aan_tables(ft, it);
-  for (int i = 0; i < 64; i++)
-  {
-    if (lut && !(std::isfinite(lut[i]) && lut[i] != 0.0f))
-      return fail(MDCT_INVALID_PARAMETER, "quantisation table entry %d is %g; the int16 paths need finite non-zero entries", i, (double)lut[i]);
-    tb.qf[i] = lut ? (1.0f / lut[i]) * ft[i] : ft[i];
-    tb.dq[i] = lut ? lut[i] * it[i] : it[i];
-  }
-  if (pair_order)
-  {
-    static const int pa[4] = {0, 2, 5, 1}, pb[4] = {4, 6, 3, 7}; // the pairs aan_fwd_h produces (mdct_kernels.hip)
-    mdct::OwnTables t = tb;
-    for (int v = 0; v < 8; v++)
-      for (int j = 0; j < 4; j++)
-      {
-        tb.qf[(j * 8 + v) * 2] = t.qf[v * 8 + pa[j]];
-        tb.qf[(j * 8 + v) * 2 + 1] = t.qf[v * 8 + pb[j]];
-        tb.dq[(j * 8 + v) * 2] = t.dq[v * 8 + pa[j]];
-        tb.dq[(j * 8 + v) * 2 + 1] = t.dq[v * 8 + pb[j]];
-      }
-  }
+  const int bad = mdct::own_tables_fill(lut, tb, pair_order);
+  if (bad >= 0)
+    return fail(MDCT_INVALID_PARAMETER, "quantisation table entry %d is %g; the int16 paths need finite non-zero entries", bad, (double)lut[bad]);
   return MDCT_SUCCESS;
 }
 
@@ -633,7 +589,7 @@ int run_f32(int mode, const float *from, float *to, size_t pitch_in, size_t pitc
     return r;
   {
     float ft[64], it[64];
-    aan_tables(ft, it);
+    mdct::aan_tables(ft, it);
     memcpy(a.scale, mode == mdct::MODE_FWD ? ft : it, sizeof(a.scale));
   }
   const hipError_t e = mdct::launch_f32(a, mode, (hipStream_t)stream);

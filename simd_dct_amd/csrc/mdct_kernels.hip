@@ -27,11 +27,13 @@
 #include "pack_rows.h"
 #include "mdct_kernels.h"
 #include "scan_records.h"
+#include "aan_fwd.h"
 
 #pragma clang fp contract(off)
 
 namespace mdct
 {
+#ifndef MDCT_AAN_FWD_ONLY // (see the region below)
 
 // The seven butterfly constants (simd_dct.cpp:140-146) travel in the kernarg segment
 // (DctConsts, mdct_kernels.h) and therefore live in SGPRs: a VALU op with an SGPR operand is
@@ -136,17 +138,6 @@ __device__ __forceinline__ void raw_inv(const DctConsts &C, float (&b)[8][8])
 // No register moves anywhere.  Written as inline asm: the compiler folds only trivial
 // shuffles into op_sel and materialises the rest as v_mov / extra packed ops.
 // ---------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-#define MDCT_PKA(d, a, b, mods) asm("v_pk_add_f32 %0, %1, %2 " mods : "=v"(d) : "v"(a), "v"(b))
-#define MDCT_PKM(d, a, k, mods) asm("v_pk_mul_f32 %0, %1, %2 " mods : "=v"(d) : "v"(a), "s"(k))
-#define MDCT_PKF(d, a, k, c, mods) asm("v_pk_fma_f32 %0, %1, %2, %3 " mods : "=v"(d) : "v"(a), "s"(k), "v"(c)) // d = a * k + c, one rounding
-// halves of the constant operand (src1) used for (lo, hi) of the result
-#define MDCT_K_LL "op_sel:[0,0] op_sel_hi:[1,0]"
-#define MDCT_K_HH "op_sel:[0,1] op_sel_hi:[1,1]"
-#define MDCT_K_LH "op_sel:[0,0] op_sel_hi:[1,1]"
-#define MDCT_K_HL "op_sel:[0,1] op_sel_hi:[1,0]"
-#define MDCT_X "op_sel:[0,1] op_sel_hi:[1,0]" // lo = a.lo (+) b.hi, hi = a.hi (+) b.lo
-#define MDCT_NEG_B "neg_lo:[0,1] neg_hi:[0,1]"  // a - b in both halves
 
 struct PkConsts
 {
@@ -367,30 +358,6 @@ __device__ __forceinline__ int32_t clamp255(int32_t v) { return min(max(v, 0), 2
 // ---------------------------------------------------------------------------------------
 // u8 forward + quantise + reorder.
 // ---------------------------------------------------------------------------------------
-// 8 pixels of one block row.  The reference takes any alignment (unaligned loads,
-// simd_dct.cpp:2109); so does this: gfx950 global loads are alignment-free in hardware, the
-// type below only stops the compiler from assuming 8-byte alignment.  Streamed once -> nt.
-typedef unsigned int u32x2_unaligned __attribute__((ext_vector_type(2), aligned(1)));
-__device__ __forceinline__ uint2 load8(const uint8_t *p)
-{
-  const u32x2_unaligned v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_unaligned *>(p));
-  return make_uint2(v.x, v.y);
-}
-
-// byte N of a dword -> float in ONE instruction (v_cvt_f32_ubyteN).  Written as (pure,
-// schedulable) inline asm, not as (float)((w >> 8N) & 0xFF): from the latter LLVM rewrites the
-// first butterfly stage as integer SDWA adds followed by v_cvt_f32_i32 (exact, but ~1.6x the
-// issue cycles on gfx950, where SDWA forms and converts are half rate).
-template <int N>
-__device__ __forceinline__ float ubyte_to_float(uint32_t w)
-{
-  float f;
-  if constexpr (N == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(f) : "v"(w));
-  else if constexpr (N == 1) asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(f) : "v"(w));
-  else if constexpr (N == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(f) : "v"(w));
-  else asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(f) : "v"(w));
-  return f;
-}
 
 // the lane's block as eight 8-byte rows, all eight loads in flight together
 __device__ __forceinline__ void load_block_rows(const uint8_t *src, size_t pitch, uint2 (&rows)[8])
@@ -1039,7 +1006,6 @@ __device__ __forceinline__ uint32_t rne_i16_bits(const DctConsts &C, float v)
 // float to an integer.  One operation fewer per coefficient pair in the packed forms, and the quantised value is the correctly rounded one.
 // The clamp works on the biased value: its bounds 1.5 * 2^23 - 32768 and + 32767 are exact floats.  Same operations as the CPU checker
 // (its quant_i16).  Low 16 bits of the result = the two's-complement int16.
-constexpr float kMagic23 = 12582912.0f, kQLo = kMagic23 - 32768.0f, kQHi = kMagic23 + 32767.0f;
 __device__ __forceinline__ uint32_t quant_i16_bits(const DctConsts &C, float y, float qf)
 {
   return __float_as_uint(__builtin_amdgcn_fmed3f(__builtin_fmaf(y, qf, C.magic23), kQLo, kQHi));
@@ -1103,25 +1069,11 @@ __device__ __forceinline__ void i16_block(const DctConsts &C, const Rows rows, c
   }
 }
 
-// The AAN butterflies on packed fp32 (fused round trip; profiles/r02_exp_i16_packed.log).  Same idea as the u8
-// tiers above: rows "horizontally" on 4 register pairs with op_sel / neg modifiers, columns "vertically" on pairs of
-// columns.  AAN's flow graph leaves 6 (forward) / 12 (inverse) operations per horizontal transform without a
-// partner; they stay scalar.  Every packed or scalar operation is the individually rounded IEEE operation of
-// aan_fwd8 / aan_inv8, so the results are bit-identical (and are tested as such against the CPU checker).
-// The first ten floats of DctConsts are laid out as the pairs these functions consume.
-struct AanPk
-{
-  f32x2 c707_382;   // (cos(pi/4), cos(3pi/8))
-  f32x2 c541_1306;  // (cos(pi/8)-cos(3pi/8), cos(pi/8)+cos(3pi/8))
-  f32x2 c1414_1847; // (sqrt 2, 2cos(pi/8))
-  f32x2 c1082_2613;
-  f32x2 magic;      // (1.5*2^23, 1.5*2^29)
-};
-static_assert(offsetof(DctConsts, c707) == 0 && offsetof(DctConsts, c382) == 4 && offsetof(DctConsts, c541) == 8 && offsetof(DctConsts, c1306) == 12 &&
-                  offsetof(DctConsts, c1414) == 16 && offsetof(DctConsts, c1847) == 20 && offsetof(DctConsts, c1082) == 24 && offsetof(DctConsts, c2613) == 28 &&
-                  offsetof(DctConsts, magic23) == 32 && offsetof(DctConsts, magic29) == 36,
-              "AanPk views the head of DctConsts");
+#endif // !MDCT_AAN_FWD_ONLY
 
+// ---- MDCT_AAN_FWD_ONLY region: from here to the matching marker below is ALL that jpeg_encode_scan.hip compiles of this file
+// (it defines MDCT_AAN_FWD_ONLY and includes this file after aan_fwd.h): the AAN passes, the quantiser and the zig-zag compaction of
+// the fused pixels -> Huffman rows kernels.  The text stays here because tests/test_asm_blocks.py proves the asm blocks from this file.
 #define MDCT_LOLO "op_sel:[0,0] op_sel_hi:[0,0]"
 #define MDCT_HIHI "op_sel:[1,1] op_sel_hi:[1,1]"
 #define MDCT_LOHI "op_sel:[0,1] op_sel_hi:[0,1]" // src0.lo with src1.hi, for both halves
@@ -1398,6 +1350,73 @@ __device__ __forceinline__ void aan_inv_h(const AanPk &K, f32x2 i04, f32x2 i26, 
 #endif
 }
 
+// ---------------------------------------------------------------------------------------
+// The back half of the fused pixels -> Huffman rows kernels, after the row passes left the block in P (aan_fwd_h).
+// ---------------------------------------------------------------------------------------
+// Column passes and quantiser: quantised levels as the low 16 bits of val[] (natural order v*8+u): the DC like the int16 plane would
+// hold it (sat_i16), the AC coefficients saturated to the +-1023 of baseline categories 1..10 -- exactly what the staged coder does to
+// an int16 record at token time.  qf: the 32 multiplier pairs in the pair order of the column pass (make_own_tables, pair_order), in
+// the kernel's argument segment; dc_shift: 64 * 128 with the level shift (exactly "raw DC minus 64 * 128"), else 0.
+// CLAMP = false: the caller knows that no level can leave those ranges, and the 64 saturations per block are left out.
+template <bool CLAMP>
+__device__ __forceinline__ void fwd_v_quant_levels(const AanPk &K, f32x2 (&P)[4][8], karg_pairs_t qf, float dc_shift, uint32_t (&val)[64])
+{
+  constexpr int kA[4] = {0, 2, 5, 1}, kB[4] = {4, 6, 3, 7};
+  const f32x2 magic_v = K.magic;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+  {
+    aan_fwd_v(K, P[j]);
+    if (j == 0)
+      P[0][0].x = P[0][0].x - dc_shift;
+    // the 8 multiplier pairs of column pair j, fetched here (all 64 multipliers held in SGPRs from the top of the kernel spilled)
+    karg_pairs_t tq = qf + j * 8;
+    asm volatile("" : "+s"(tq));
+#pragma unroll
+    for (int v = 0; v < 8; v++)
+    {
+      f32x2 c;
+      MDCT_PKF(c, P[j][v], tq[v], magic_v, "op_sel:[0,0,0] op_sel_hi:[1,1,0]"); // quant_i16_bits; the clamps (baseline JPEG: AC to +-1023) on the biased value
+      const bool is_dc = j == 0 && v == 0;
+      if constexpr (CLAMP)
+        c = f32x2{__builtin_amdgcn_fmed3f(c.x, is_dc ? kQLo : kMagic23 - 1023.0f, is_dc ? kQHi : kMagic23 + 1023.0f), __builtin_amdgcn_fmed3f(c.y, kMagic23 - 1023.0f, kMagic23 + 1023.0f)};
+      val[v * 8 + kA[j]] = __float_as_uint(c.x);
+      val[v * 8 + kB[j]] = __float_as_uint(c.y);
+    }
+  }
+}
+
+// Zig-zag order; AC entries run << 12 | level compacted to the front of the lane's LDS row rec (kRec16Row halfwords), a ZRL entry for
+// every 16 zeros in a row.  EVERY coefficient writes run << 12 | level at the current position and only those that need an entry
+// advance it: a zero's write is overwritten by the next entry -- unless it is the 16th zero in a row, and then what it
+// wrote, 15 << 12 | 0, IS the ZRL entry.  (7 vector instructions per coefficient; selecting value and address per
+// coefficient and tracking the last non-zero took 11.)  Returns the number of entries; ZRL entries after the last coefficient are
+// dropped (at most three: 62 zeros).  my_dc: the DC level; need_eob: position 63 is not coded.
+__device__ __forceinline__ uint32_t compact_levels16(const uint32_t (&val)[64], uint16_t *rec, int &my_dc, bool &need_eob)
+{
+  uint32_t pos = 0, r12 = 0;
+#pragma unroll
+  for (int k = 1; k < 64; k++)
+  {
+    const uint32_t v = val[kZigZag[k]];
+    const bool nz = (v & 0xFFFFu) != 0;
+    const bool wr = nz || r12 == 0xF000u;
+    rec[pos] = (uint16_t)((v & 0xFFFu) | r12);
+    pos += wr ? 1u : 0u;
+    r12 = wr ? 0u : r12 + 0x1000u;
+  }
+  uint32_t n = pos;
+#pragma unroll
+  for (int t = 0; t < 3; t++)
+    n -= (n > 0 && rec[n - 1] == 0xF000u) ? 1u : 0u;
+  my_dc = (int)(int16_t)(val[0] & 0xFFFFu);
+  need_eob = (val[kZigZag[63]] & 0xFFFFu) == 0;
+  return n;
+}
+
+// ---- end of the MDCT_AAN_FWD_ONLY region
+#ifndef MDCT_AAN_FWD_ONLY
+
 // quantise -> dequantise of the eight pairs of one column pair, SAT-free: c = rne(y qf) by the fused magic add (quant_i16_bits) and the subtract, z = c dq
 __device__ __forceinline__ void quant_dequant8(const AanPk &K, f32x2 (&p)[8], const f32x2 (&qf)[8], const f32x2 (&dq)[8])
 {
@@ -1442,17 +1461,9 @@ __device__ __forceinline__ void quant_dequant8(const AanPk &K, f32x2 (&p)[8], co
 // DCT coefficient of int16 samples is at most 8 * 32768 in magnitude -- so the two saturations per coefficient pair are left out.
 // tbp: where the plane's OwnTables lie -- in the kernel's argument segment (karg_bytes) or in device memory (const_bytes); read with
 // scalar loads either way
-typedef const __attribute__((address_space(4))) char *kbytes_t;
 template <bool HAS_LUT, class Rows, bool PRIO = false, bool SAT = true>
 __device__ __forceinline__ void i16_roundtrip_rows(const DctConsts &C, const Rows rows, kbytes_t tbp);
 
-// The two tables are 128 multiplier pairs = 256 SGPRs if the compiler is left to fetch them when it likes -- it fetches
-// them all at the top and spills (252 v_readlane + 124 v_writelane per wave, 1451 vector instructions instead of ~1000).
-// So the pairs of column pair j are read from the argument segment through a pointer the compiler cannot see through,
-// right where they are used: two s_load_dwordx16 per j, 32 SGPRs live (mdct_api.hip lays the tables out j-major for this).
-typedef const __attribute__((address_space(4))) f32x2 *karg_pairs_t;
-__device__ __forceinline__ kbytes_t karg_bytes(size_t byte_off) { return (kbytes_t)__builtin_amdgcn_kernarg_segment_ptr() + byte_off; }
-__device__ __forceinline__ karg_pairs_t karg_pairs(size_t byte_off) { return (karg_pairs_t)karg_bytes(byte_off); }
 // a wave-uniform device address as a constant-address-space pointer (scalar loads; the memory must not change during the launch)
 __device__ __forceinline__ kbytes_t const_bytes(const void *p)
 {
@@ -2152,55 +2163,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_px_huffman_rows(PxHuffArgs a)
       }
       aan_fwd_h(K, a01, a23, a45, a67, P[0][r], P[1][r], P[2][r], P[3][r]);
     }
-    // quantised levels as the low 16 bits of val[]: the DC like the int16 plane would hold it (sat_i16), the AC coefficients
-    // saturated to the +-1023 of baseline categories 1..10 -- exactly what the staged coder does to an int16 record at token time
+    // ---- column passes, quantiser, zig-zag compaction into the lane's LDS row (the MDCT_AAN_FWD_ONLY region above)
     uint32_t val[64];
-    constexpr int kA[4] = {0, 2, 5, 1}, kB[4] = {4, 6, 3, 7};
-    const f32x2 magic_v = K.magic;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-    {
-      aan_fwd_v(K, P[j]);
-      if (j == 0)
-        P[0][0].x = P[0][0].x - a.dc_shift; // the level shift is exactly "raw DC minus 64 * 128"
-      // the 8 multiplier pairs of column pair j, fetched here (all 64 multipliers held in SGPRs from the top of the kernel spilled)
-      karg_pairs_t tq = karg_pairs(offsetof(PxHuffArgs, tb) + offsetof(OwnTables, qf)) + j * 8;
-      asm volatile("" : "+s"(tq));
-#pragma unroll
-      for (int v = 0; v < 8; v++)
-      {
-        f32x2 c;
-        MDCT_PKF(c, P[j][v], tq[v], magic_v, "op_sel:[0,0,0] op_sel_hi:[1,1,0]"); // quant_i16_bits; the clamps (baseline JPEG: AC to +-1023) on the biased value
-        const bool is_dc = j == 0 && v == 0;
-        if constexpr (CLAMP)
-          c = f32x2{__builtin_amdgcn_fmed3f(c.x, is_dc ? kQLo : kMagic23 - 1023.0f, is_dc ? kQHi : kMagic23 + 1023.0f), __builtin_amdgcn_fmed3f(c.y, kMagic23 - 1023.0f, kMagic23 + 1023.0f)};
-        val[v * 8 + kA[j]] = __float_as_uint(c.x);
-        val[v * 8 + kB[j]] = __float_as_uint(c.y);
-      }
-    }
-    // ---- zig-zag order; AC entries run << 12 | level compacted to the front of the lane's LDS row, a ZRL entry for every
-    // 16 zeros in a row.  EVERY coefficient writes run << 12 | level at the current position and only those that need an entry
-    // advance it: a zero's write is overwritten by the next entry -- unless it is the 16th zero in a row, and then what it
-    // wrote, 15 << 12 | 0, IS the ZRL entry.  (7 vector instructions per coefficient; selecting value and address per
-    // coefficient and tracking the last non-zero took 11.)
-    uint32_t pos = 0, r12 = 0;
-#pragma unroll
-    for (int k = 1; k < 64; k++)
-    {
-      const uint32_t v = val[kZigZag[k]];
-      const bool nz = (v & 0xFFFFu) != 0;
-      const bool wr = nz || r12 == 0xF000u;
-      rec[pos] = (uint16_t)((v & 0xFFFu) | r12);
-      pos += wr ? 1u : 0u;
-      r12 = wr ? 0u : r12 + 0x1000u;
-    }
-    // ZRL entries after the last coefficient are dropped (at most three: 62 zeros)
-    uint32_t n = pos;
-#pragma unroll
-    for (int t = 0; t < 3; t++)
-      n -= (n > 0 && rec[n - 1] == 0xF000u) ? 1u : 0u;
-    const int my_dc = (int)(int16_t)(val[0] & 0xFFFFu);
-    const bool need_eob = (val[kZigZag[63]] & 0xFFFFu) == 0;
+    fwd_v_quant_levels<CLAMP>(K, P, karg_pairs(offsetof(PxHuffArgs, tb) + offsetof(OwnTables, qf)), a.dc_shift, val);
+    int my_dc;
+    bool need_eob;
+    const uint32_t n = compact_levels16(val, rec, my_dc, need_eob);
     if (c0 + kChunk < a.bpr)
       fetch(bx + kChunk); // in flight while this chunk is coded
     coder.chunk(c0, rec, (int)n, live, my_dc, need_eob);
@@ -2800,4 +2768,5 @@ hipError_t launch_stream_copy(const void *from, void *to, size_t bytes, int cus,
   return hipGetLastError();
 }
 
+#endif // !MDCT_AAN_FWD_ONLY
 } // namespace mdct

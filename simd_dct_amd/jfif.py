@@ -4,7 +4,8 @@ The device produces, per component plane, one unstuffed byte-aligned Huffman seg
 (restart interval = one block row, ITU-T T.81 E.1.4).  This module does what remains to obtain a
 baseline JPEG any decoder opens: byte stuffing (B.1.1.5), RSTm markers between the rows, and the
 marker segments (B.2: SOI, APP0/JFIF, DQT, SOF0, DHT, DRI, SOS, EOI).  One non-interleaved scan per
-component, so a 4:2:0 picture is three scans (Y at full resolution, Cb / Cr at half).
+component, so a 4:2:0 picture is three scans (Y at full resolution, Cb / Cr at half) -- or, given the
+scan of libmdct_jpegenc_scan.so, one interleaved scan (write_jpeg's `interleaved`).
 No reference counterpart (the reference stops at the coefficient reorder, simd_dct.cpp:2221-2230).
 """
 import struct
@@ -42,7 +43,7 @@ def scan_bytes(segments, seg_bytes, seg_stride):
     return b"".join(out)
 
 
-def write_jpeg(components, width, height, specs=None, sampling=None):
+def write_jpeg(components, width, height, specs=None, sampling=None, interleaved=None):
     """components: list of 1 (grey) or 3 (Y, Cb, Cr with Cb/Cr at half resolution) dicts with keys
          'blocks_per_row', 'qtable' (64 integers 1..255, natural order v*8+u) and either
          'scan' (bytes / uint8 array: the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it) or
@@ -51,6 +52,10 @@ def write_jpeg(components, width, height, specs=None, sampling=None):
          blocks per side of the component's true size ceil(width * h / hmax) x ceil(height * v / vmax) (T.81 A.2.2)
        specs: {which: (bits16, vals)} Huffman specifications (default: the library's, api.huffman_spec)
        sampling: [(h, v)] per component (default: (2, 2), (1, 1), (1, 1) for three components, (1, 1) for one)
+       interleaved: None, or dict(scan=..., mcus_per_row=...) for three components: ONE scan whose MCUs interleave the components
+         (T.81 A.2.3) replaces the per-component scans -- one DRI (= MCUs per row, the scan's restart interval), one SOS naming all
+         three components (Y: tables 0/0, Cb and Cr: 1/1), the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it.  The
+         components then need 'qtable' only.
        Returns the file as bytes."""
     specs = specs or {w: api.huffman_spec(w) for w in range(4)}
     zz = api.zigzag_table()
@@ -70,6 +75,12 @@ def write_jpeg(components, width, height, specs=None, sampling=None):
         sof += bytes([ci + 1, (h << 4) | v, min(ci, 1)])
     f.append(_seg(0xC0, sof))
     f.append(_seg(0xC4, _dht(0, 0, *specs[0]) + _dht(1, 0, *specs[1]) + (_dht(0, 1, *specs[2]) + _dht(1, 1, *specs[3]) if nc == 3 else b"")))
+    if interleaved is not None:
+        assert nc == 3, "an interleaved scan takes three components"
+        f.append(_seg(0xDD, struct.pack(">H", interleaved["mcus_per_row"])))
+        f.append(_seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
+        f.append(bytes(memoryview(np.ascontiguousarray(interleaved["scan"]))))
+        components = []
     for ci, c in enumerate(components):
         f.append(_seg(0xDD, struct.pack(">H", c["blocks_per_row"])))
         th = 0 if ci == 0 else 1

@@ -4,11 +4,14 @@ include/mdct.h).  The mirror of jpeg_decode.decode_jpeg.
 encode_jpeg runs one launch of mdct_jpegenc_from_rgb (RGB -> YCbCr, chroma downsampling and padding to the block grid, as
 libjpeg-turbo's compressor does them), then one restart-marked scan per component (mdct_fwd_u8_huffman_rows and
 mdct_jpeg_pack_rows_counted: pixels -> stuffed scan with RSTm between the block rows, Annex K tables), copies back the scans' lengths and bytes and writes the marker segments (jfif.write_jpeg).
+With interleaved=True a colour image becomes ONE scan whose MCUs interleave the components, the form every other encoder writes
+(libmdct_jpegenc_scan.so, include/mdct_jpegenc_scan.h: mdct_jpegenc_scan_rows codes the three planes, padded to the MCU grid, in
+MCU order; one packing launch and one read-back instead of three).
 torch is used for device memory and streams only.
 """
 import numpy as np
 
-from . import _jpegenc_lib, api, jfif
+from . import _jpegenc_lib, _jpegenc_scan_lib, api, jfif
 from .api import _stream
 
 # ITU-T T.81 Annex K.1 / K.2 (natural order v*8+u)
@@ -57,6 +60,13 @@ def component_sizes(width, height, sampling):
         cw, ch = _ceil(width * h, hmax), _ceil(height * v, vmax)
         out.append((cw, ch, _ceil(cw, 8) * 8, _ceil(ch, 8) * 8))
     return out
+
+
+def mcu_grid(width, height, sampling):
+    """(mcus_x, mcus_y, [(padded width, padded height)] per component on the MCU grid: mcus_x * 8 * h x mcus_y * 8 * v)"""
+    hmax, vmax = max(h for h, _ in sampling), max(v for _, v in sampling)
+    mx, my = _ceil(width, 8 * hmax), _ceil(height, 8 * vmax)
+    return mx, my, [(mx * 8 * h, my * 8 * v) for h, v in sampling]
 
 
 def last_error():
@@ -121,6 +131,58 @@ def to_planes(image, subsampling="4:2:0", layout="HWC", planes=None, stream=None
     return planes
 
 
+def scan_seg_stride(mcus_x, sampling):
+    """smallest legal seg_stride of scan_rows (mdct_jpegenc_scan_seg_stride)"""
+    return int(_jpegenc_scan_lib.load().mdct_jpegenc_scan_seg_stride(mcus_x, sum(h * v for h, v in sampling)))
+
+
+def scan_rows(planes, sampling, luts, out, seg_bytes, ff_counts, seg_stride=None, my0=0, my1=None, stream=None, check=True):
+    """mdct_jpegenc_scan_rows on device tensors.  planes: Y, Cb, Cr, uint8 [rows, columns] with contiguous columns, each exactly its size
+    on the MCU grid (mcu_grid); sampling: [(h, v)] per component; luts: (luma, chroma), 64 numbers each in natural order.  out: uint8,
+    one segment per MCU row seg_stride apart (default: scan_seg_stride); seg_bytes / ff_counts: int32 per MCU row.  MCU rows my0 .. my1
+    (default: all) are coded.  Returns the status (raises unless check=False)."""
+    arr = (_jpegenc_scan_lib.Plane * max(1, len(planes)))()
+    for k, (p, (h, v)) in enumerate(zip(planes, sampling)):
+        if p.dim() != 2 or p.stride(1) != 1 or p.element_size() != 1:
+            raise ValueError(f"plane {k}: uint8 tensor [rows, columns] with contiguous columns")
+        arr[k] = _jpegenc_scan_lib.Plane(p.data_ptr(), p.stride(0), p.shape[1], p.shape[0], h, v)
+    tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+    mcus_x, mcus_y = planes[-1].shape[1] // 8, planes[-1].shape[0] // 8
+    if seg_stride is None:
+        seg_stride = scan_seg_stride(mcus_x, sampling)
+    lib = _jpegenc_scan_lib.load()
+    rc = lib.mdct_jpegenc_scan_rows(arr, len(planes), tabs[0].ctypes.data, tabs[1].ctypes.data, my0, mcus_y if my1 is None else my1, out.data_ptr(), seg_stride,
+                                    seg_bytes.data_ptr(), ff_counts.data_ptr(), _stream(stream))
+    if check and rc != 0:
+        raise api.MdctError(f"mdct_jpegenc_scan status {rc}: {lib.mdct_jpegenc_scan_last_error().decode()}")
+    return rc
+
+
+def _first_capacity(pixels):
+    """bytes of the first scan buffer: ~0.2 bytes per pixel in practice; a scan that does not fit is coded again into its worst case"""
+    return pixels + 4096
+
+
+def _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, tabs, stream):
+    """the colour image as one interleaved scan: front launch into planes on the MCU grid, scan_rows, the packing launch, one read-back"""
+    dev = image.device
+    mcus_x, mcus_y, sizes = mcu_grid(W, H, sampling)
+    planes = to_planes(image, subsampling, layout, planes=[torch.empty((ph, pw), dtype=torch.uint8, device=dev) for pw, ph in sizes], stream=stream)
+    stride = scan_seg_stride(mcus_x, sampling)
+    seg = torch.empty((mcus_y * stride,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((2, mcus_y), dtype=torch.int32, device=dev)
+    off = torch.empty((mcus_y + 1,), dtype=torch.int64, device=dev)
+    scan_rows(planes, sampling, (tabs[0], tabs[1]), seg, counts[0], counts[1], seg_stride=stride, stream=stream)
+    out = torch.empty((_first_capacity(sum(pw * ph for pw, ph in sizes)),), dtype=torch.uint8, device=dev)
+    api.jpeg_pack_rows(seg, counts[0], stride, mcus_y, out, off, ff_counts=counts[1], stream=stream)
+    end = int(off[-1].item())  # the one copy that waits for the scan
+    if end > out.numel():  # the segments are there: only the packing runs again, into the worst case
+        out = torch.empty((2 * mcus_y * stride,), dtype=torch.uint8, device=dev)
+        api.jpeg_pack_rows(seg, counts[0], stride, mcus_y, out, off, ff_counts=counts[1], stream=stream)
+        end = int(off[-1].item())
+    return dict(scan=out[:end].cpu().numpy(), mcus_per_row=mcus_x)
+
+
 class _Scan:
     """device buffers of one component's scan"""
 
@@ -144,7 +206,7 @@ def _run_scan(plane, pw, ph, lut, chroma, sc, two_launch, stream):
                              stream=stream)
 
 
-def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True):
+def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True, interleaved=False):
     """Encode an 8-bit image as a baseline JPEG (JFIF) on the GPU and return the file as bytes.
 
     image: uint8 [H, W, 3] (layout="HWC"), [3, H, W] (layout="CHW") or [H, W] (grey, any layout); a numpy array or CPU tensor is
@@ -156,10 +218,17 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     its scan, with no front launch.  Each component is then one non-interleaved scan over its own block grid, with the Annex K Huffman
     tables and a restart marker after every block row (DRI = blocks per row, first marker RST0), made by mdct_fwd_u8_huffman_rows and
     mdct_jpeg_pack_rows_counted (two_launch=False: one launch of mdct_fwd_u8_jpeg_scan per component, the same bytes; 9 % slower at
-    8192x8192 4:2:0).  Only the scans' lengths and bytes are copied back."""
+    8192x8192 4:2:0).  Only the scans' lengths and bytes are copied back.
+
+    interleaved=True (a bool): a colour image is written as ONE scan whose MCUs interleave the components (T.81 A.2.3; DRI = MCUs per
+    row), the form cameras, libjpeg-turbo and hardware coders write: the planes are padded to the MCU grid, mdct_jpegenc_scan_rows
+    codes them in MCU order and one packing launch finishes the scan (two_launch plays no part).  A grey
+    image has one component, whose scan is non-interleaved by definition: the argument changes nothing there."""
     import torch
 
     q = _quality(quality)
+    if not isinstance(interleaved, (bool, np.bool_)):
+        raise ValueError(f"interleaved {interleaved!r}: a bool")
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
             raise ValueError(f"image dtype {image.dtype}: uint8")
@@ -176,6 +245,9 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
         image = image.to(dev)
     dev = image.device
     with torch.cuda.device(dev):
+        if interleaved and not grey:
+            scan = _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, (luma, chroma), stream)
+            return jfif.write_jpeg([dict(qtable=luma), dict(qtable=chroma), dict(qtable=chroma)], W, H, sampling=sampling, interleaved=scan)
         if grey and W % 8 == 0 and H % 8 == 0 and image.stride(1) == 1:
             planes = [image]
         else:

@@ -1,5 +1,7 @@
 """Example: a baseline JPEG written by the engine's stages (tools/ = not part of the product path).
-    python3 tools/gpu_jpeg.py out.jpg [synthetic | synthetic-color | raw_grey_file] [X Y]
+    python3 tools/gpu_jpeg.py out.jpg [synthetic | synthetic-color | synthetic-interleaved | raw_grey_file] [X Y]
+synthetic-interleaved: an RGB image through jpeg_encode.encode_jpeg(interleaved=True) -- ONE scan whose MCUs interleave Y, Cb, Cr (4:2:0, quality 75),
+the file every other decoder expects (libmdct_jpegenc_scan.so); MDCT_JPEG_SUBSAMPLING=4:4:4 | 4:2:2 selects another sampling.
 Default (round 3), grey: ONE launch, pixels -> finished scan (mdct_fwd_u8_jpeg_scan).  Colour: per plane the fused pixels -> Huffman rows
 kernel (mdct_fwd_i16_huffman_rows), then mdct_jpeg_pack_rows_counted -- three one-launch encoders side by side on three streams wait on each
 other's rows and measure 2 % slower (MDCT_JPEG_ONE_LAUNCH=1 selects them anyway; MDCT_JPEG_TWO_LAUNCH=1 the two launches for grey too).
@@ -24,6 +26,18 @@ out = sys.argv[1] if len(sys.argv) > 1 else "out.jpg"
 src = sys.argv[2] if len(sys.argv) > 2 else "synthetic"
 W, H = (int(sys.argv[3]), int(sys.argv[4])) if len(sys.argv) > 4 else (4096, 2160 - 2160 % 16)
 M.init(0)
+
+if src == "synthetic-interleaved":
+    from simd_dct_amd import jpeg_encode
+    sub = os.environ.get("MDCT_JPEG_SUBSAMPLING", "4:2:0")
+    rgb = torch.stack([synth.plane_u8_torch(W, H, "photo", seed=s) for s in (5, 6, 7)], dim=-1).contiguous()
+    data = jpeg_encode.encode_jpeg(rgb, quality=75, subsampling=sub, interleaved=True)  # warm
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    data = jpeg_encode.encode_jpeg(rgb, quality=75, subsampling=sub, interleaved=True)
+    dt = time.perf_counter() - t0
+    open(out, "wb").write(data)
+    print(f"{W}x{H} {sub} colour, one interleaved scan: {dt * 1e3:.2f} ms to the file's bytes, {len(data)} bytes ({8 * len(data) / (W * H):.2f} bit/px) -> {out}")
+    sys.exit(0)
 
 
 class Plane:

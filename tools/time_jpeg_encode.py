@@ -1,7 +1,9 @@
 """Times the encoder's front stage (libmdct_jpegenc.so, mdct_jpegenc_from_rgb) on full frames, next to mdct_split420_u8_planes on the
 same frame in the same process (it moves the same 4.5 B per pixel at 4:2:0), and encode_jpeg of an 8192x8192 RGB image at q75 4:2:0
 in both scan forms (the fused coder + counted packing, the default, or one launch per component), with the wall clock to the returned bytes split
-into device work, the length readback and the copy of the scans, next to Pillow's encode of the same image on one host core.
+into device work, the length readback and the copy of the scans, next to Pillow's encode of the same image on one host core; and the
+one-interleaved-scan form (encode_jpeg(interleaved=True), libmdct_jpegenc_scan.so) against the three-scan form on the same images,
+taken alternately in one process: device time of the whole path, the scan coder alone against the three launches it replaces, wall time.
 
 Each case runs in a child process of its own under `timeout`; the parent prints one JSON line per case.  Front-stage times are
 HIP-event medians of 5 repetitions of 20 back-to-back launches, per launch; encode times are medians of 5 calls.  Kernel times come
@@ -28,7 +30,14 @@ FRONT_CASES = {
     "front-7680x4320-420-hwc": (7680, 4320, "4:2:0", "HWC"),
     "front-7680x4320-444-hwc": (7680, 4320, "4:4:4", "HWC"),
 }
-CASES = list(FRONT_CASES) + ["encode-8192-420-q75"]
+# one interleaved scan (libmdct_jpegenc_scan.so) against the three-scan path on the same image, alternating: name -> (W, H, subsampling)
+INTERLEAVED_CASES = {
+    "interleaved-8192-420-q75": (8192, 8192, "4:2:0"),
+    "interleaved-8192-444-q75": (8192, 8192, "4:4:4"),
+    "interleaved-7680x4320-420-q75": (7680, 4320, "4:2:0"),
+    "interleaved-7680x4320-444-q75": (7680, 4320, "4:4:4"),
+}
+CASES = list(FRONT_CASES) + ["encode-8192-420-q75"] + list(INTERLEAVED_CASES)
 REPS, LAUNCHES = 5, 20
 
 
@@ -127,6 +136,93 @@ def encode_case(name):
     return res
 
 
+def interleaved_case(name):
+    """device time (events, per repetition: front launch + scans + packing) of the interleaved path and of the three-scan path
+    (interleaved=False, two_launch=True), taken alternately on the same planes' image; the scan coder alone against the three
+    mdct_fwd_u8_huffman_rows launches it replaces; wall time of encode_jpeg both ways.  HWC, quality 75, synth "photo" content."""
+    import numpy as np
+    import torch
+
+    from simd_dct_amd import api, synth
+    from simd_dct_amd import jpeg_encode as J
+
+    api.init(0)
+    W, H, sub = INTERLEAVED_CASES[name]
+    host = np.stack([synth.plane_u8_np(W, H, "photo", seed=31 + k) for k in range(3)], axis=-1)
+    img = torch.from_numpy(host).cuda()
+    sampling = J.sampling_of(sub)
+    luma, chroma = J.quality_tables(75)
+    # the three-scan path's buffers
+    sizes = J.component_sizes(W, H, sampling)
+    planes3 = J.to_planes(img, sub, "HWC")
+    scans = [J._Scan(torch, img.device, pw, ph, pw * ph + 4096) for _, _, pw, ph in sizes]
+    # the interleaved path's
+    mx, my, msizes = J.mcu_grid(W, H, sampling)
+    planes1 = [torch.empty((ph, pw), dtype=torch.uint8, device="cuda") for pw, ph in msizes]
+    stride = J.scan_seg_stride(mx, sampling)
+    seg = torch.empty((my * stride,), dtype=torch.uint8, device="cuda")
+    counts = torch.empty((2, my), dtype=torch.int32, device="cuda")
+    off = torch.empty((my + 1,), dtype=torch.int64, device="cuda")
+    out = torch.empty((sum(pw * ph for pw, ph in msizes) + 4096,), dtype=torch.uint8, device="cuda")
+
+    def three_rows():
+        for k, (p, (_, _, pw, ph), sc) in enumerate(zip(planes3, sizes, scans)):
+            api.fwd_u8_huffman_rows(p, pw, ph, sc.seg, sc.counts[0], lut=luma if k == 0 else chroma, chroma=k > 0, seg_stride=sc.stride, pitch=p.stride(0),
+                                    ff_counts=sc.counts[1])
+
+    def three():
+        J.to_planes(img, sub, "HWC", planes=planes3)
+        for k, (p, (_, _, pw, ph), sc) in enumerate(zip(planes3, sizes, scans)):
+            J._run_scan(p, pw, ph, luma if k == 0 else chroma, k > 0, sc, True, None)
+
+    def one_rows():
+        J.scan_rows(planes1, sampling, (luma, chroma), seg, counts[0], counts[1], seg_stride=stride)
+
+    def one():
+        J.to_planes(img, sub, "HWC", planes=planes1)
+        one_rows()
+        api.jpeg_pack_rows(seg, counts[0], stride, my, out, off, ff_counts=counts[1])
+
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn):
+        start.record()
+        fn()
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) * 1000.0
+
+    for fn in (three, one, three, one):  # warm: code objects, tables
+        fn()
+    torch.cuda.synchronize()
+    t = dict(three=[], one=[], three_rows=[], one_rows=[])
+    for _ in range(2 * REPS + 1):  # alternating
+        t["three"].append(timed(three))
+        t["one"].append(timed(one))
+        t["three_rows"].append(timed(three_rows))
+        t["one_rows"].append(timed(one_rows))
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    assert int(off[-1].item()) <= out.numel()
+    wall = dict(three=[], one=[])
+    for form, flag in (("three", False), ("one", True), ("three", False), ("one", True)):
+        J.encode_jpeg(img, quality=75, subsampling=sub, interleaved=flag)
+    files = {}
+    for _ in range(REPS):
+        for form, flag in (("three", False), ("one", True)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            files[form] = J.encode_jpeg(img, quality=75, subsampling=sub, interleaved=flag)
+            wall[form].append((time.perf_counter() - t0) * 1e6)
+    res = dict(case=name, width=W, height=H, subsampling=sub, mcus=[mx, my], kernels=sorted(k for k in api.kernel_counts() if k.startswith("k_scan_rows")))
+    for k, label in (("three", "three_scan"), ("one", "interleaved")):
+        res[label] = dict(device_us=round(med[k], 1), device_min_max_us=[round(min(t[k]), 1), round(max(t[k]), 1)], device_reps_us=[round(x, 1) for x in t[k]],
+                          rows_us=round(med[k + "_rows"], 1), rows_min_max_us=[round(min(t[k + "_rows"]), 1), round(max(t[k + "_rows"]), 1)],
+                          wall_us=round(sorted(wall[k])[len(wall[k]) // 2], 1), wall_reps_us=[round(x, 1) for x in wall[k]], file_bytes=len(files[k]))
+    res["interleaved_over_three_scan_device"] = round(med["one"] / med["three"], 4)
+    res["inside_three_scan_spread"] = bool(med["one"] <= max(t["three"]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", choices=CASES)
@@ -134,7 +230,7 @@ def main():
     ap.add_argument("--timeout", type=int, default=300)
     a = ap.parse_args()
     if a.case:
-        res = encode_case(a.case) if a.case.startswith("encode") else front_case(a.case)
+        res = encode_case(a.case) if a.case.startswith("encode") else interleaved_case(a.case) if a.case in INTERLEAVED_CASES else front_case(a.case)
         print(json.dumps(res), flush=True)
         return 0
     lines, rc = [], 0
