@@ -7,11 +7,14 @@ mdct_jpeg_pack_rows_counted: pixels -> stuffed scan with RSTm between the block 
 With interleaved=True a colour image becomes ONE scan whose MCUs interleave the components, the form every other encoder writes
 (libmdct_jpegenc_scan.so, include/mdct_jpegenc_scan.h: mdct_jpegenc_scan_rows codes the three planes, padded to the MCU grid, in
 MCU order; one packing launch and one read-back instead of three).
+With optimize=True the Huffman tables are made for the image (T.81 K.2, libjpeg's optimize_coding; libmdct_jpegenc_opt.so,
+include/mdct_jpegenc_opt.h): symbol_histogram counts the symbols the coder will emit, optimal_tables builds the tables on the host and
+the coders of that library take them in place of the Annex K ones.
 torch is used for device memory and streams only.
 """
 import numpy as np
 
-from . import _jpegenc_lib, _jpegenc_scan_lib, api, jfif
+from . import _jpegenc_lib, _jpegenc_opt_lib, _jpegenc_scan_lib, api, jfif
 from .api import _stream
 
 # ITU-T T.81 Annex K.1 / K.2 (natural order v*8+u)
@@ -158,21 +161,143 @@ def scan_rows(planes, sampling, luts, out, seg_bytes, ff_counts, seg_stride=None
     return rc
 
 
+def _opt_error(rc):
+    lib = _jpegenc_opt_lib.load()
+    return api.MdctError(f"mdct_jpegenc_opt status {rc}: {lib.mdct_jpegenc_opt_last_error().decode()}")
+
+
+def _plane_array(planes, sampling):
+    arr = (_jpegenc_scan_lib.Plane * max(1, len(planes)))()
+    for k, (p, (h, v)) in enumerate(zip(planes, sampling)):
+        if p.dim() != 2 or p.stride(1) != 1 or p.element_size() != 1:
+            raise ValueError(f"plane {k}: uint8 tensor [rows, columns] with contiguous columns")
+        arr[k] = _jpegenc_scan_lib.Plane(p.data_ptr(), p.stride(0), p.shape[1], p.shape[0], h, v)
+    return arr
+
+
+def symbol_histogram(planes, sampling, luts, interleaved=False, hist=None, stream=None, check=True):
+    """mdct_jpegenc_opt_stats on device tensors: the counts of the Huffman symbols that the coder of these planes and tables emits.
+    planes: 1 (grey) or 3 (Y, Cb, Cr) uint8 [rows, columns] with contiguous columns -- interleaved=False: each on its own block grid
+    (component_sizes), every plane a scan of its own with a restart interval per block row; interleaved=True: on the MCU grid (mcu_grid),
+    one scan in MCU order with a restart interval per MCU row.  sampling: [(h, v)] per component; luts: (luma, chroma), 64 numbers each.
+    hist: int32 device tensor [2, 272] (allocated if None), zeroed by the call itself: class 0 luminance, 1 chrominance; entries 0..15 the
+    DC categories, 16 + RRRRSSSS the AC symbols.  Returns hist (with check=False: (status, hist))."""
+    import torch
+
+    if not isinstance(interleaved, (bool, np.bool_)):
+        raise ValueError(f"interleaved {interleaved!r}: a bool")
+    arr = _plane_array(planes, sampling)
+    tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+    if hist is None:
+        hist = torch.empty((2, _jpegenc_opt_lib.HIST_CLASS), dtype=torch.int32, device=planes[0].device)
+    if hist.dtype != torch.int32 or tuple(hist.shape) != (2, _jpegenc_opt_lib.HIST_CLASS) or not hist.is_contiguous():
+        raise ValueError("hist: a contiguous int32 tensor [2, 272]")
+    rc = _jpegenc_opt_lib.load().mdct_jpegenc_opt_stats(arr, len(planes), tabs[0].ctypes.data, tabs[-1].ctypes.data, int(interleaved), hist.data_ptr(), _stream(stream))
+    if check and rc != 0:
+        raise _opt_error(rc)
+    return hist if check else (rc, hist)
+
+
+def optimal_table(counts):
+    """mdct_jpegenc_opt_table (host): libjpeg's optimal Huffman table for the counts of one class (12..16 DC categories or 256 AC
+    symbols) -> (bits16, vals)"""
+    c = np.ascontiguousarray(np.asarray(counts).astype(np.uint32))
+    bits = np.zeros(16, dtype=np.uint8)
+    vals = np.zeros(256, dtype=np.uint8)
+    n = _jpegenc_opt_lib.c_int()
+    rc = _jpegenc_opt_lib.load().mdct_jpegenc_opt_table(c.ctypes.data, c.size, bits.ctypes.data, vals.ctypes.data, n)
+    if rc != 0:
+        raise _opt_error(rc)
+    return bits.tolist(), vals[:n.value].tolist()
+
+
+def optimal_tables(hist, grey=False):
+    """hist of symbol_histogram (a device tensor is copied to the host: that waits for the stream) -> {which: (bits16, vals)} keyed like
+    api.huffman_spec: 0 DC luminance, 1 AC luminance, 2 DC chrominance, 3 AC chrominance (grey: 0 and 1 only)"""
+    h = np.asarray(hist.cpu() if hasattr(hist, "cpu") else hist).astype(np.int64).reshape(2, _jpegenc_opt_lib.HIST_CLASS) & 0xFFFFFFFF
+    out = {}
+    for cls in range(1 if grey else 2):
+        out[2 * cls] = optimal_table(h[cls, :16])
+        out[2 * cls + 1] = optimal_table(h[cls, 16:])
+    return out
+
+
+class _Specs:
+    """{which: (bits16, vals)} as the mdct_jpegenc_opt_spec array of the coders (keeps the host arrays alive)"""
+
+    def __init__(self, specs, which):
+        self.keep = []
+        self.arr = (_jpegenc_opt_lib.Spec * len(which))()
+        for k, w in enumerate(which):
+            bits, vals = specs[w]
+            b, v = np.ascontiguousarray(np.asarray(bits, dtype=np.uint8)), np.ascontiguousarray(np.asarray(vals, dtype=np.uint8))
+            if b.shape != (16,) or v.ndim != 1:
+                raise ValueError(f"specification {w}: (16 counts, values)")
+            self.keep += [b, v]
+            self.arr[k] = _jpegenc_opt_lib.Spec(b.ctypes.data, v.ctypes.data, v.size)
+
+
+def opt_seg_stride(blocks):
+    """smallest legal seg_stride of opt_rows / opt_scan_rows for segments of `blocks` blocks (mdct_jpegenc_opt_seg_stride)"""
+    return int(_jpegenc_opt_lib.load().mdct_jpegenc_opt_seg_stride(blocks))
+
+
+def opt_rows(plane, lut, specs, out, seg_bytes, ff_counts, uncoded, seg_stride=None, by0=0, by1=None, stream=None, check=True):
+    """mdct_jpegenc_opt_rows on device tensors: one plane (uint8 [rows, columns], multiples of 8, contiguous columns) -> one segment per
+    block row, coded with specs = (DC (bits16, vals), AC (bits16, vals)).  uncoded: an int32 device tensor of one element that the
+    caller has zeroed; the call adds the number of symbols the tables have no code for.  Otherwise as api.fwd_u8_huffman_rows."""
+    if plane.dim() != 2 or plane.stride(1) != 1 or plane.element_size() != 1:
+        raise ValueError("plane: uint8 tensor [rows, columns] with contiguous columns")
+    sp = _Specs({0: specs[0], 1: specs[1]}, (0, 1))
+    tab = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(64))
+    ph, pw = plane.shape
+    if seg_stride is None:
+        seg_stride = opt_seg_stride(pw // 8)
+    rc = _jpegenc_opt_lib.load().mdct_jpegenc_opt_rows(plane.data_ptr(), plane.stride(0), tab.ctypes.data, pw, ph, by0, ph // 8 if by1 is None else by1, sp.arr[0], sp.arr[1],
+                                                       out.data_ptr(), seg_stride, seg_bytes.data_ptr(), ff_counts.data_ptr(), uncoded.data_ptr(), _stream(stream))
+    if check and rc != 0:
+        raise _opt_error(rc)
+    return rc
+
+
+def opt_scan_rows(planes, sampling, luts, specs, out, seg_bytes, ff_counts, uncoded, seg_stride=None, my0=0, my1=None, stream=None, check=True):
+    """mdct_jpegenc_opt_scan_rows on device tensors: scan_rows with specs = {which: (bits16, vals)} keyed like api.huffman_spec in place of
+    the Annex K tables, seg_stride at least opt_seg_stride(blocks per MCU row), and uncoded as for opt_rows."""
+    arr = _plane_array(planes, sampling)
+    sp = _Specs(specs, (0, 1, 2, 3))
+    tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+    mcus_x, mcus_y = planes[-1].shape[1] // 8, planes[-1].shape[0] // 8
+    if seg_stride is None:
+        seg_stride = opt_seg_stride(mcus_x * sum(h * v for h, v in sampling))
+    rc = _jpegenc_opt_lib.load().mdct_jpegenc_opt_scan_rows(arr, len(planes), tabs[0].ctypes.data, tabs[1].ctypes.data, sp.arr, my0, mcus_y if my1 is None else my1,
+                                                            out.data_ptr(), seg_stride, seg_bytes.data_ptr(), ff_counts.data_ptr(), uncoded.data_ptr(), _stream(stream))
+    if check and rc != 0:
+        raise _opt_error(rc)
+    return rc
+
+
 def _first_capacity(pixels):
     """bytes of the first scan buffer: ~0.2 bytes per pixel in practice; a scan that does not fit is coded again into its worst case"""
     return pixels + 4096
 
 
-def _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, tabs, stream):
-    """the colour image as one interleaved scan: front launch into planes on the MCU grid, scan_rows, the packing launch, one read-back"""
+def _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, tabs, stream, optimize=False):
+    """the colour image as one interleaved scan: front launch into planes on the MCU grid, scan_rows, the packing launch, one read-back.
+    optimize: the statistics launch and the wait for its histogram first, then opt_scan_rows with the tables made from it"""
     dev = image.device
     mcus_x, mcus_y, sizes = mcu_grid(W, H, sampling)
     planes = to_planes(image, subsampling, layout, planes=[torch.empty((ph, pw), dtype=torch.uint8, device=dev) for pw, ph in sizes], stream=stream)
-    stride = scan_seg_stride(mcus_x, sampling)
+    stride = opt_seg_stride(mcus_x * sum(h * v for h, v in sampling)) if optimize else scan_seg_stride(mcus_x, sampling)
     seg = torch.empty((mcus_y * stride,), dtype=torch.uint8, device=dev)
     counts = torch.empty((2, mcus_y), dtype=torch.int32, device=dev)
     off = torch.empty((mcus_y + 1,), dtype=torch.int64, device=dev)
-    scan_rows(planes, sampling, (tabs[0], tabs[1]), seg, counts[0], counts[1], seg_stride=stride, stream=stream)
+    specs = None
+    if optimize:
+        specs = optimal_tables(symbol_histogram(planes, sampling, tabs, interleaved=True, stream=stream))  # the copy that waits for the histogram
+        uncoded = torch.zeros((1,), dtype=torch.int32, device=dev)
+        opt_scan_rows(planes, sampling, tabs, specs, seg, counts[0], counts[1], uncoded, seg_stride=stride, stream=stream)
+    else:
+        scan_rows(planes, sampling, (tabs[0], tabs[1]), seg, counts[0], counts[1], seg_stride=stride, stream=stream)
     out = torch.empty((_first_capacity(sum(pw * ph for pw, ph in sizes)),), dtype=torch.uint8, device=dev)
     api.jpeg_pack_rows(seg, counts[0], stride, mcus_y, out, off, ff_counts=counts[1], stream=stream)
     end = int(off[-1].item())  # the one copy that waits for the scan
@@ -180,15 +305,17 @@ def _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, tabs,
         out = torch.empty((2 * mcus_y * stride,), dtype=torch.uint8, device=dev)
         api.jpeg_pack_rows(seg, counts[0], stride, mcus_y, out, off, ff_counts=counts[1], stream=stream)
         end = int(off[-1].item())
-    return dict(scan=out[:end].cpu().numpy(), mcus_per_row=mcus_x)
+    if optimize and int(uncoded.item()) != 0:
+        raise api.MdctError(f"{int(uncoded.item())} symbols of the scan have no code in the tables made for it")
+    return dict(scan=out[:end].cpu().numpy(), mcus_per_row=mcus_x), specs
 
 
 class _Scan:
     """device buffers of one component's scan"""
 
-    def __init__(self, torch, dev, pw, ph, capacity):
+    def __init__(self, torch, dev, pw, ph, capacity, optimize=False):
         rows = ph // 8
-        self.stride = api.huffman_seg_stride(pw)
+        self.stride = opt_seg_stride(pw // 8) if optimize else api.huffman_seg_stride(pw)
         self.seg = torch.empty((rows * self.stride,), dtype=torch.uint8, device=dev)
         self.out = torch.empty((capacity,), dtype=torch.uint8, device=dev)
         self.off = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
@@ -196,8 +323,11 @@ class _Scan:
         self.counts = torch.empty((2, rows), dtype=torch.int32, device=dev)  # the two-launch form's byte and 0xFF counts
 
 
-def _run_scan(plane, pw, ph, lut, chroma, sc, two_launch, stream):
-    if two_launch:
+def _run_scan(plane, pw, ph, lut, chroma, sc, two_launch, stream, specs=None, uncoded=None):
+    if specs is not None:  # optimize: the caller's tables, always the two-launch form
+        opt_rows(plane, lut, (specs[2 if chroma else 0], specs[3 if chroma else 1]), sc.seg, sc.counts[0], sc.counts[1], uncoded, seg_stride=sc.stride, stream=stream)
+        api.jpeg_pack_rows(sc.seg, sc.counts[0], sc.stride, ph // 8, sc.out, sc.off, ff_counts=sc.counts[1], stream=stream)
+    elif two_launch:
         api.fwd_u8_huffman_rows(plane, pw, ph, sc.seg, sc.counts[0], lut=lut, chroma=chroma, seg_stride=sc.stride, pitch=plane.stride(0),
                                 ff_counts=sc.counts[1], stream=stream)
         api.jpeg_pack_rows(sc.seg, sc.counts[0], sc.stride, ph // 8, sc.out, sc.off, ff_counts=sc.counts[1], stream=stream)
@@ -206,7 +336,7 @@ def _run_scan(plane, pw, ph, lut, chroma, sc, two_launch, stream):
                              stream=stream)
 
 
-def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True, interleaved=False):
+def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True, interleaved=False, optimize=False):
     """Encode an 8-bit image as a baseline JPEG (JFIF) on the GPU and return the file as bytes.
 
     image: uint8 [H, W, 3] (layout="HWC"), [3, H, W] (layout="CHW") or [H, W] (grey, any layout); a numpy array or CPU tensor is
@@ -223,12 +353,21 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     interleaved=True (a bool): a colour image is written as ONE scan whose MCUs interleave the components (T.81 A.2.3; DRI = MCUs per
     row), the form cameras, libjpeg-turbo and hardware coders write: the planes are padded to the MCU grid, mdct_jpegenc_scan_rows
     codes them in MCU order and one packing launch finishes the scan (two_launch plays no part).  A grey
-    image has one component, whose scan is non-interleaved by definition: the argument changes nothing there."""
+    image has one component, whose scan is non-interleaved by definition: the argument changes nothing there.
+
+    optimize=True (a bool): the Huffman tables are made for this image (T.81 K.2, what libjpeg's optimize_coding and Pillow's
+    optimize=True do; typically a tenth fewer bytes, the same coefficients): after the front launch one statistics launch counts the
+    symbols the coder will emit (symbol_histogram), its 2176 bytes are copied back -- a second wait besides the one for the scan --, the
+    tables (one luminance and one chrominance pair, whatever the scan form) are built on the host (optimal_tables), and the coders of
+    libmdct_jpegenc_opt.so write the segments with them (two_launch plays no part); the file carries the tables in its DHT segment.
+    DESIGN.md section 4.9.2."""
     import torch
 
     q = _quality(quality)
     if not isinstance(interleaved, (bool, np.bool_)):
         raise ValueError(f"interleaved {interleaved!r}: a bool")
+    if not isinstance(optimize, (bool, np.bool_)):
+        raise ValueError(f"optimize {optimize!r}: a bool")
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
             raise ValueError(f"image dtype {image.dtype}: uint8")
@@ -246,24 +385,33 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     dev = image.device
     with torch.cuda.device(dev):
         if interleaved and not grey:
-            scan = _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, (luma, chroma), stream)
-            return jfif.write_jpeg([dict(qtable=luma), dict(qtable=chroma), dict(qtable=chroma)], W, H, sampling=sampling, interleaved=scan)
+            scan, specs = _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, (luma, chroma), stream, optimize)
+            return jfif.write_jpeg([dict(qtable=luma), dict(qtable=chroma), dict(qtable=chroma)], W, H, specs=specs, sampling=sampling, interleaved=scan)
         if grey and W % 8 == 0 and H % 8 == 0 and image.stride(1) == 1:
             planes = [image]
         else:
             planes = to_planes(image, subsampling, layout, stream=stream)
         tabs = [luma] + [chroma] * (len(planes) - 1)
+        specs = uncoded = None
+        if optimize:
+            specs = optimal_tables(symbol_histogram(planes, sampling, (luma, chroma), stream=stream), grey=grey)  # the copy that waits for the histogram
+            uncoded = torch.zeros((1,), dtype=torch.int32, device=dev)
         # ~0.2 bytes per pixel in practice; a scan that does not fit is coded again into its worst case
-        scans = [_Scan(torch, dev, pw, ph, pw * ph + 4096) for _, _, pw, ph in sizes]
+        scans = [_Scan(torch, dev, pw, ph, _first_capacity(pw * ph), optimize) for _, _, pw, ph in sizes]
         for k, (p, (_, _, pw, ph), sc) in enumerate(zip(planes, sizes, scans)):
-            _run_scan(p, pw, ph, tabs[k], k > 0, sc, two_launch, stream)
+            _run_scan(p, pw, ph, tabs[k], k > 0, sc, two_launch, stream, specs, uncoded)
         ends = torch.stack([sc.off[-1] for sc in scans]).cpu().tolist()  # the one copy that waits for the scans
         for k, (p, (_, _, pw, ph), sc) in enumerate(zip(planes, sizes, scans)):
             if ends[k] < 0:  # UINT64_MAX read as int64
                 raise api.MdctError(f"scan {k}: the one-launch coder reported a failure (row_offsets = UINT64_MAX)")
             if ends[k] > sc.out.numel():
                 sc.out = torch.empty((2 * (ph // 8) * sc.stride,), dtype=torch.uint8, device=dev)
-                _run_scan(p, pw, ph, tabs[k], k > 0, sc, two_launch, stream)
+                if optimize:  # the segments are there: only the packing runs again
+                    api.jpeg_pack_rows(sc.seg, sc.counts[0], sc.stride, ph // 8, sc.out, sc.off, ff_counts=sc.counts[1], stream=stream)
+                else:
+                    _run_scan(p, pw, ph, tabs[k], k > 0, sc, two_launch, stream)
                 ends[k] = int(sc.off[-1].item())
+        if optimize and int(uncoded.item()) != 0:
+            raise api.MdctError(f"{int(uncoded.item())} symbols of the scans have no code in the tables made for them")
         comps = [dict(scan=sc.out[:n].cpu().numpy(), blocks_per_row=pw // 8, qtable=t) for sc, n, (_, _, pw, _), t in zip(scans, ends, sizes, tabs)]
-    return jfif.write_jpeg(comps, W, H, sampling=sampling)
+    return jfif.write_jpeg(comps, W, H, specs=specs, sampling=sampling)

@@ -1,5 +1,6 @@
 """Example: a baseline JPEG written by the engine's stages (tools/ = not part of the product path).
-    python3 tools/gpu_jpeg.py out.jpg [synthetic | synthetic-color | synthetic-interleaved | raw_grey_file] [X Y]
+    python3 tools/gpu_jpeg.py out.jpg [synthetic | synthetic-color | synthetic-interleaved | raw_grey_file] [X Y] [--optimize]
+--optimize (synthetic-interleaved): Huffman tables made for the image, encode_jpeg(optimize=True) (libmdct_jpegenc_opt.so).
 synthetic-interleaved: an RGB image through jpeg_encode.encode_jpeg(interleaved=True) -- ONE scan whose MCUs interleave Y, Cb, Cr (4:2:0, quality 75),
 the file every other decoder expects (libmdct_jpegenc_scan.so); MDCT_JPEG_SUBSAMPLING=4:4:4 | 4:2:2 selects another sampling.
 Default (round 3), grey: ONE launch, pixels -> finished scan (mdct_fwd_u8_jpeg_scan).  Colour: per plane the fused pixels -> Huffman rows
@@ -16,6 +17,9 @@ import numpy as np, torch
 import simd_dct_amd as M
 from simd_dct_amd import jfif, synth
 
+OPTIMIZE = "--optimize" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--optimize"]
+
 K1 = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
                18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99], dtype=np.float32)
 K2 = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32, dtype=np.float32)
@@ -31,12 +35,12 @@ if src == "synthetic-interleaved":
     from simd_dct_amd import jpeg_encode
     sub = os.environ.get("MDCT_JPEG_SUBSAMPLING", "4:2:0")
     rgb = torch.stack([synth.plane_u8_torch(W, H, "photo", seed=s) for s in (5, 6, 7)], dim=-1).contiguous()
-    data = jpeg_encode.encode_jpeg(rgb, quality=75, subsampling=sub, interleaved=True)  # warm
+    data = jpeg_encode.encode_jpeg(rgb, quality=75, subsampling=sub, interleaved=True, optimize=OPTIMIZE)  # warm
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    data = jpeg_encode.encode_jpeg(rgb, quality=75, subsampling=sub, interleaved=True)
+    data = jpeg_encode.encode_jpeg(rgb, quality=75, subsampling=sub, interleaved=True, optimize=OPTIMIZE)
     dt = time.perf_counter() - t0
     open(out, "wb").write(data)
-    print(f"{W}x{H} {sub} colour, one interleaved scan: {dt * 1e3:.2f} ms to the file's bytes, {len(data)} bytes ({8 * len(data) / (W * H):.2f} bit/px) -> {out}")
+    print(f"{W}x{H} {sub} colour, one interleaved scan{', optimised tables' if OPTIMIZE else ''}: {dt * 1e3:.2f} ms to the file's bytes, {len(data)} bytes ({8 * len(data) / (W * H):.2f} bit/px) -> {out}")
     sys.exit(0)
 
 

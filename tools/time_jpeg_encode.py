@@ -3,7 +3,9 @@ same frame in the same process (it moves the same 4.5 B per pixel at 4:2:0), and
 in both scan forms (the fused coder + counted packing, the default, or one launch per component), with the wall clock to the returned bytes split
 into device work, the length readback and the copy of the scans, next to Pillow's encode of the same image on one host core; and the
 one-interleaved-scan form (encode_jpeg(interleaved=True), libmdct_jpegenc_scan.so) against the three-scan form on the same images,
-taken alternately in one process: device time of the whole path, the scan coder alone against the three launches it replaces, wall time.
+taken alternately in one process: device time of the whole path, the scan coder alone against the three launches it replaces, wall time;
+and encode_jpeg(optimize=True) (libmdct_jpegenc_opt.so) against optimize=False in both scan forms: device time, the statistics launch
+alone, the wait for the histogram, wall time and file sizes.
 
 Each case runs in a child process of its own under `timeout`; the parent prints one JSON line per case.  Front-stage times are
 HIP-event medians of 5 repetitions of 20 back-to-back launches, per launch; encode times are medians of 5 calls.  Kernel times come
@@ -37,7 +39,14 @@ INTERLEAVED_CASES = {
     "interleaved-7680x4320-420-q75": (7680, 4320, "4:2:0"),
     "interleaved-7680x4320-444-q75": (7680, 4320, "4:4:4"),
 }
-CASES = list(FRONT_CASES) + ["encode-8192-420-q75"] + list(INTERLEAVED_CASES)
+# encode_jpeg(optimize=True) (libmdct_jpegenc_opt.so) against optimize=False on the same image, alternating: name -> (W, H, subsampling, interleaved)
+OPTIMIZED_CASES = {
+    "optimized-8192-420-q75-three": (8192, 8192, "4:2:0", False),
+    "optimized-8192-420-q75-interleaved": (8192, 8192, "4:2:0", True),
+    "optimized-7680x4320-444-q75-three": (7680, 4320, "4:4:4", False),
+    "optimized-7680x4320-444-q75-interleaved": (7680, 4320, "4:4:4", True),
+}
+CASES = list(FRONT_CASES) + ["encode-8192-420-q75"] + list(INTERLEAVED_CASES) + list(OPTIMIZED_CASES)
 REPS, LAUNCHES = 5, 20
 
 
@@ -223,6 +232,112 @@ def interleaved_case(name):
     return res
 
 
+def optimized_case(name):
+    """device time (events, buffers kept: front launch + coder(s) + packing, with optimize also the statistics launch and the coders
+    of libmdct_jpegenc_opt.so with the image's tables) with and without optimize, taken alternately on the same image, 11 repetitions;
+    the statistics launch(es) alone and the Annex K coder launch(es) alone on the same planes; the wait for the histogram (the copy of
+    its 2176 bytes after the statistics launch, wall clock); wall time of encode_jpeg to bytes and the file sizes both ways."""
+    import numpy as np
+    import torch
+
+    from simd_dct_amd import api, synth
+    from simd_dct_amd import jpeg_encode as J
+
+    api.init(0)
+    W, H, sub, inter = OPTIMIZED_CASES[name]
+    host = np.stack([synth.plane_u8_np(W, H, "photo", seed=31 + k) for k in range(3)], axis=-1)
+    img = torch.from_numpy(host).cuda()
+    sampling = J.sampling_of(sub)
+    luts = J.quality_tables(75)
+    bpm = sum(h * v for h, v in sampling)
+    if inter:
+        mx, my, msizes = J.mcu_grid(W, H, sampling)
+        sizes = [(pw, ph) for pw, ph in msizes]
+        rows = [(my, mx * bpm)]
+    else:
+        sizes = [(pw, ph) for _, _, pw, ph in J.component_sizes(W, H, sampling)]
+        rows = [(ph // 8, pw // 8) for pw, ph in sizes]
+    planes = [torch.empty((ph, pw), dtype=torch.uint8, device="cuda") for pw, ph in sizes]
+    J.to_planes(img, sub, "HWC", planes=planes)
+    hist = torch.empty((2, 272), dtype=torch.int32, device="cuda")
+    specs = J.optimal_tables(J.symbol_histogram(planes, sampling, luts, interleaved=inter, hist=hist))
+    uncoded = torch.zeros((1,), dtype=torch.int32, device="cuda")
+    # per scan: segments at the Annex K stride and at the stride of the coders that take tables, counts, the packed scan, offsets
+    bufs = []
+    for n, blocks in rows:
+        st0, st1 = 208 * blocks + 8, J.opt_seg_stride(blocks)
+        bufs.append(dict(n=n, st0=st0, st1=st1, seg=torch.empty((n * st1,), dtype=torch.uint8, device="cuda"), counts=torch.empty((2, n), dtype=torch.int32, device="cuda"),
+                         out=torch.empty((n * blocks * 64 + 4096,), dtype=torch.uint8, device="cuda"), off=torch.empty((n + 1,), dtype=torch.int64, device="cuda")))
+
+    def stats():
+        J.symbol_histogram(planes, sampling, luts, interleaved=inter, hist=hist)
+
+    def coders(opt):
+        for k, b in enumerate(bufs):
+            if inter:
+                if opt:
+                    J.opt_scan_rows(planes, sampling, luts, specs, b["seg"], b["counts"][0], b["counts"][1], uncoded, seg_stride=b["st1"])
+                else:
+                    J.scan_rows(planes, sampling, luts, b["seg"], b["counts"][0], b["counts"][1], seg_stride=b["st0"])
+            elif opt:
+                J.opt_rows(planes[k], luts[min(k, 1)], (specs[2 * min(k, 1)], specs[2 * min(k, 1) + 1]), b["seg"], b["counts"][0], b["counts"][1], uncoded, seg_stride=b["st1"])
+            else:
+                pw, ph = sizes[k]
+                api.fwd_u8_huffman_rows(planes[k], pw, ph, b["seg"], b["counts"][0], lut=luts[min(k, 1)], chroma=k > 0, seg_stride=b["st0"], pitch=planes[k].stride(0),
+                                        ff_counts=b["counts"][1])
+
+    def whole(opt):
+        J.to_planes(img, sub, "HWC", planes=planes)
+        if opt:
+            stats()
+        coders(opt)
+        for b in bufs:
+            api.jpeg_pack_rows(b["seg"], b["counts"][0], b["st1"] if opt else b["st0"], b["n"], b["out"], b["off"], ff_counts=b["counts"][1])
+
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn):
+        start.record()
+        fn()
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) * 1000.0
+
+    for _ in range(2):  # warm: code objects, tables
+        whole(False)
+        whole(True)
+    torch.cuda.synchronize()
+    t = dict(plain=[], optimize=[], stats=[], plain_coders=[], optimize_coders=[], hist_wait=[])
+    for _ in range(2 * REPS + 1):  # alternating
+        t["plain"].append(timed(lambda: whole(False)))
+        t["optimize"].append(timed(lambda: whole(True)))
+        t["stats"].append(timed(stats))
+        t["plain_coders"].append(timed(lambda: coders(False)))
+        t["optimize_coders"].append(timed(lambda: coders(True)))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        stats()
+        hist.cpu()
+        t["hist_wait"].append((time.perf_counter() - t0) * 1e6)
+    assert int(uncoded.item()) == 0 and all(int(b["off"][-1].item()) <= b["out"].numel() for b in bufs)
+    wall, files = dict(plain=[], optimize=[]), {}
+    for flag in (False, True, False, True):
+        J.encode_jpeg(img, quality=75, subsampling=sub, interleaved=inter, optimize=flag)
+    for _ in range(2 * REPS + 1):
+        for form, flag in (("plain", False), ("optimize", True)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            files[form] = J.encode_jpeg(img, quality=75, subsampling=sub, interleaved=inter, optimize=flag)
+            wall[form].append((time.perf_counter() - t0) * 1e6)
+    t.update(plain_wall=wall["plain"], optimize_wall=wall["optimize"])
+    res = dict(case=name, width=W, height=H, subsampling=sub, interleaved=inter, kernels=sorted(k for k in api.kernel_counts() if k.startswith("k_opt")))
+    for k, v in t.items():
+        res[k + "_us"] = dict(median=round(sorted(v)[len(v) // 2], 1), min_max=[round(min(v), 1), round(max(v), 1)], reps=[round(x, 1) for x in v])
+    res.update(plain_file_bytes=len(files["plain"]), optimize_file_bytes=len(files["optimize"]), size_ratio=round(len(files["optimize"]) / len(files["plain"]), 4),
+               stats_no_longer_than_the_coders=bool(res["stats_us"]["median"] <= res["plain_coders_us"]["median"]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", choices=CASES)
@@ -230,7 +345,8 @@ def main():
     ap.add_argument("--timeout", type=int, default=300)
     a = ap.parse_args()
     if a.case:
-        res = encode_case(a.case) if a.case.startswith("encode") else interleaved_case(a.case) if a.case in INTERLEAVED_CASES else front_case(a.case)
+        res = (encode_case(a.case) if a.case.startswith("encode") else interleaved_case(a.case) if a.case in INTERLEAVED_CASES
+               else optimized_case(a.case) if a.case in OPTIMIZED_CASES else front_case(a.case))
         print(json.dumps(res), flush=True)
         return 0
     lines, rc = [], 0
