@@ -138,12 +138,17 @@ def check_i16_fwd_vs_double(src, got, W, H, lut, by0=0, by1=None, u8_shift=None)
     want = np.clip(np.rint(ref / q), -32768, 32767)
     d = np.abs(got.astype(np.float64) - want)[by0 * 8:by1 * 8]
     assert d.max() <= 1, ("int16 forward vs double", float(d.max()))
+    # and the exact rule wherever the window decides (tests/test_fdct_accuracy.py chooses inputs that it mostly does; these full-scale
+    # planes are taken as they are, so no floor on the decided share here)
+    rows = slice(by0 * 8, by1 * 8)
+    R.check_planes("fwd_u8" if u8_shift else "fwd_i16", [np.asarray(src)[rows]], [np.asarray(got)[rows]], [lut], min_decided=0.0)
 
 
 def check_f32_vs_double(src, got, W, H):
     want = O.f32("f64ref", src, W, H)
     rel = np.abs(_blocks(got.astype(np.float64), W, H) - _blocks(want, W, H)).max(1) / np.maximum(np.abs(_blocks(want, W, H)).max(1), 1e-30)
     assert rel.max() < 1e-5, float(rel.max())
+    R.check_planes("fwd_f32", [src], [got], [None])
 
 
 def check_inv_vs_double(kind, src, got, W, H, lut, by0=0, by1=None, level_shift=True):
