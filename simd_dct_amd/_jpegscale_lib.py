@@ -1,0 +1,50 @@
+"""ctypes binding of libmdct_jpegscale.so -- the C-ABI declared in include/mdct_jpegscale.h (the reduced-size inverse of a JPEG decode:
+coefficient planes -> 8-bit planes at 1/2, 1/4 or 1/8 size on the GPU).
+
+Its own signature table: a separate library, linked against libmdct_hip.so.  No fallback: if the shared object is missing or fails to
+load, every entry point raises.
+"""
+import ctypes
+import os
+
+from . import _lib
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libmdct_jpegscale.so")
+
+c_size_t = ctypes.c_size_t
+c_void_p = ctypes.c_void_p
+c_int = ctypes.c_int
+
+
+class Plane(ctypes.Structure):
+    """mdct_jpegscale_plane"""
+
+    _fields_ = [("coef", c_void_p), ("pitch_coef", c_size_t), ("px", c_void_p), ("pitch_px", c_size_t), ("blocks_x", c_size_t),
+                ("blocks_y", c_size_t), ("lut", c_void_p), ("n", c_int), ("rep_x", c_int), ("rep_y", c_int)]
+
+
+# name -> (restype, argtypes); every function include/mdct_jpegscale.h declares
+SIGNATURES = {
+    "mdct_jpegscale_inv_i16_u8": (c_int, [ctypes.POINTER(Plane), c_int, c_int, c_void_p]),
+    "mdct_jpegscale_last_error": (ctypes.c_char_p, []),
+}
+
+_lib_handle = None
+
+
+def load():
+    """Load libmdct_jpegscale.so (once), after libmdct_hip.so (whose launch tally and HIP runtime it shares)."""
+    global _lib_handle
+    if _lib_handle is not None:
+        return _lib_handle
+    _lib.load()
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
+    lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _lib_handle = lib
+    return lib

@@ -7,6 +7,9 @@ without by mdct_jpegdec_decode_unmarked.  It checks every scan's status, and run
 mdct_inv_i16_u8_batch over the planes with each component's DQT as the table.  One uint8 plane per component, cropped to the
 component's size (T.81 A.1.1).  With mode="RGB" the planes go through one more launch, mdct_jpegcolor_to_rgb
 (libmdct_jpegcolor.so, include/mdct_jpegcolor.h): chroma upsampling and YCbCr -> RGB as libjpeg-turbo's default decode gives them.
+With scale_denom = 2, 4 or 8 the picture comes out at 1/2, 1/4 or 1/8 size as libjpeg-turbo scales it (scaled_geometry): the scans are
+decoded as ever, components whose blocks shrink go through mdct_jpegscale_inv_i16_u8 (libmdct_jpegscale.so,
+include/mdct_jpegscale.h, loaded at the first such call) in place of the full inverse.
 torch is used for device memory and streams only.
 """
 import ctypes
@@ -152,15 +155,119 @@ def scan_geometry(info, scan, geo, grid):
     return grid[0], grid[1], [(c["index"], comps[c["index"]]["h"], comps[c["index"]]["v"]) for c in scan["components"]]
 
 
-def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None, layout="HWC"):
+SCALE_DENOMS = (1, 2, 4, 8)
+
+
+def scaled_geometry(info, scale_denom):
+    """libjpeg-turbo's geometry of a decode at 1 / scale_denom (1, 2, 4, 8), from read_jpeg's frame; pure Python.  With m = 8 / scale_denom
+    a component of sampling (h, v) decodes its blocks to s x s samples: s starts at m and doubles while s < 8 and
+    (hmax * m) % (h * s * 2) == 0 and (vmax * m) % (v * s * 2) == 0 (a subsampled component keeps more of its own resolution rather than
+    being upsampled afterwards).  -> ([(s, true width, true height, effective h, effective v)] per component, (image width, image
+    height)): the component is ceil(W * h * s / (hmax * 8)) x ceil(H * v * s / (vmax * 8)), the image ceil(W * m / 8) x
+    ceil(H * m / 8), and (h * s / m, v * s / m) are the sampling factors the colour stage sees."""
+    if scale_denom not in SCALE_DENOMS:
+        raise ValueError(f"scale_denom {scale_denom!r} (1, 2, 4 or 8)")
+    m = 8 // scale_denom
+    comps = info["components"]
+    W, H = info["width"], info["height"]
+    hmax, vmax = max(c["h"] for c in comps), max(c["v"] for c in comps)
+    out = []
+    for c in comps:
+        h, v, s = c["h"], c["v"], m
+        while s < 8 and (hmax * m) % (h * s * 2) == 0 and (vmax * m) % (v * s * 2) == 0:
+            s *= 2
+        out.append((s, _ceil(W * h * s, hmax * 8), _ceil(H * v * s, vmax * 8), h * s // m, v * s // m))
+    return out, (_ceil(W * m, 8), _ceil(H * m, 8))
+
+
+def scaled_last_error():
+    from . import _jpegscale_lib
+
+    return _jpegscale_lib.load().mdct_jpegscale_last_error().decode()
+
+
+def scaled_inverse(planes, level_shift=True, stream=None):
+    """mdct_jpegscale_inv_i16_u8, one launch: planes = 1..4 of (px uint8 [blocks_y * n, blocks_x * n] device tensor, coef int16
+    [blocks_y * 8, blocks_x * 8] device tensor, blocks_x, blocks_y, lut (64 floats, natural order) or None, n = 4, 2 or 1[, (rep_x,
+    rep_y): n = 1 only, every sample written rep_x x rep_y times into px [blocks_y * rep_y, blocks_x * rep_x]]); rows of either tensor
+    may lie any pitch apart, columns must be contiguous"""
+    from . import _jpegscale_lib
+
+    lib = _jpegscale_lib.load()
+    arr = (_jpegscale_lib.Plane * max(1, len(planes)))()
+    keep = []
+    for k, (px, coef, bx, by, lut, n, *more) in enumerate(planes):
+        rx, ry = more[0] if more else (1, 1)
+        if px.dim() != 2 or coef.dim() != 2 or px.stride(1) != 1 or coef.stride(1) != 1:
+            raise ValueError(f"plane {k}: [rows, columns] tensors with contiguous columns")
+        if lut is not None:
+            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(64))
+            keep.append(lut)
+        arr[k] = _jpegscale_lib.Plane(_ptr(coef), coef.stride(0), _ptr(px), px.stride(0), bx, by, None if lut is None else lut.ctypes.data, n, rx, ry)
+    rc = lib.mdct_jpegscale_inv_i16_u8(arr, len(planes), int(bool(level_shift)), _stream(stream))
+    if rc != 0:
+        raise api.MdctError(f"mdct_jpegscale status {rc}: {scaled_last_error()}")
+
+
+def colour_sampling(info, scale_denom):
+    """the sampling factors the colour stage is given after a decode at 1 / scale_denom, and the replication (rep_x, rep_y) each
+    component gets before it.  Up to 1/4 these are scaled_geometry's effective factors and no replication.  At 1/8 libjpeg-turbo
+    switches its triangle ("fancy") filters off (jdsample.c: only while the smallest block is larger than one sample) and upsamples
+    by plain replication: a component that still needs upsampling there is written replicated to the image's size by the scaled
+    inverse and then enters the colour stage at the largest factors.  -> ([(h, v)], [(rep_x, rep_y)])"""
+    sgeo, _ = scaled_geometry(info, scale_denom)
+    eff = [(g[3], g[4]) for g in sgeo]
+    hmax, vmax = max(h for h, _ in eff), max(v for _, v in eff)
+    if scale_denom != 8 or any(hmax % h or vmax % v for h, v in eff):
+        return eff, [(1, 1)] * len(eff)
+    reps = [(hmax // h, vmax // v) for h, v in eff]
+    for g, r in zip(sgeo, reps):
+        if r != (1, 1) and g[0] != 1:
+            raise jfif.JpegFormatError(f"no RGB at 1/8 for sampling factors {[(c['h'], c['v']) for c in info['components']]}")
+    return [(hmax, vmax) if r != (1, 1) else e for e, r in zip(eff, reps)], reps
+
+
+def scaled_planes(info, coefs, scale_denom, stream=None, replicate=False):
+    """the inverse stage of a decode at 1 / scale_denom (2, 4, 8): read_jpeg's frame and its quantised coefficient planes (device int16,
+    padded to the MCU grid, as geometry() sizes them) -> one uint8 plane per component, cropped to its scaled true size.  Components
+    that keep 8 x 8 blocks take mdct_inv_i16_u8_batch, the others one mdct_jpegscale_inv_i16_u8 call.  replicate=True: the planes
+    as the colour stage takes them (colour_sampling): at 1/8 a component that needs upsampling comes replicated, cropped to the image."""
+    import torch
+
+    geo, _ = geometry(info)
+    sgeo, (sw, sh) = scaled_geometry(info, scale_denom)
+    reps = colour_sampling(info, scale_denom)[1] if replicate else [(1, 1)] * len(sgeo)
+    luts = []
+    for c in info["components"]:
+        if c["tq"] not in info["qtables"]:
+            raise jfif.JpegFormatError(f"quantisation table {c['tq']} is not defined")
+        luts.append(info["qtables"][c["tq"]].astype(np.float32))
+    px = [torch.empty((g[3] * sg[0] * r[1], g[2] * sg[0] * r[0]), dtype=torch.uint8, device=q.device) for g, sg, q, r in zip(geo, sgeo, coefs, reps)]
+    full = [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, sg, lut in zip(px, coefs, geo, sgeo, luts) if sg[0] == 8]
+    small = [(p, q, g[2], g[3], lut, sg[0], r) for p, q, g, sg, lut, r in zip(px, coefs, geo, sgeo, luts, reps) if sg[0] != 8]
+    if full:
+        api.u8_i16_batch("inv", full, level_shift=True, stream=stream)
+    if small:
+        scaled_inverse(small, level_shift=True, stream=stream)
+    return [p[:sg[2], :sg[1]] if r == (1, 1) else p[:sh, :sw] for p, sg, r in zip(px, sgeo, reps)]
+
+
+def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None, layout="HWC", scale_denom=1):
     """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file).  Returns one uint8
     tensor [height, width] per component (cropped to its true size); with coefficients=True also the quantised int16 coefficient planes
     ([blocks_y * 8, blocks_x * 8], padded to the MCU grid): (planes, coefficient planes).
     mode="RGB" returns one uint8 image instead of the planes, [height, width, 3] (layout="HWC") or [3, height, width] (layout="CHW"),
     upsampled and converted as libjpeg-turbo's default decode does it (to_rgb); with coefficients=True: (image, coefficient planes).
+    scale_denom = 2, 4 or 8 returns the planes or the image at 1/2, 1/4 or 1/8 size, ceil(width / scale_denom) x
+    ceil(height / scale_denom), as libjpeg-turbo scales them (scaled_geometry; Pillow's draft): every block becomes the box mean of its
+    IDCT, and a subsampled component keeps more of its own samples before any upsampling (at 1/8 what upsampling is left is plain
+    replication, as libjpeg-turbo does it: colour_sampling).  The coefficient planes stay the full ones.
+    The entropy decode, which is most of a decode's time, is the same at every scale: the scaled picture saves memory, not much time.
     Raises jfif.JpegFormatError for a file outside the supported subset and JpegDecodeError when a scan does not decode cleanly."""
     import torch
 
+    if scale_denom not in SCALE_DENOMS:
+        raise ValueError(f"scale_denom {scale_denom!r} (1, 2, 4 or 8)")
     if mode not in (None, "RGB"):
         raise ValueError(f"mode {mode!r} (None or 'RGB')")
     if layout not in _LAYOUTS:
@@ -208,6 +315,12 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
                 k = int(bad[0])
                 raise JpegDecodeError(f"scan {si}: {bad.size} of {n} restart intervals failed; interval {k}: "
                                       f"{_jpegdec_lib.STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
+        if scale_denom != 1:
+            out = scaled_planes(info, coefs, scale_denom, stream=stream, replicate=mode == "RGB")
+            if mode == "RGB":
+                sw, sh = scaled_geometry(info, scale_denom)[1]
+                out = to_rgb(out, colour_sampling(info, scale_denom)[0], sw, sh, colour=info["colorspace"], layout=layout, stream=stream)
+            return (out, coefs) if coefficients else out
         px = [torch.empty((by * 8, bx * 8), dtype=torch.uint8, device=dev) for _, _, bx, by in geo]
         luts = []
         for c in info["components"]:
