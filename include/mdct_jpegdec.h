@@ -84,7 +84,14 @@ size_t mdct_jpegdec_intervals(const mdct_jpegdec_scan *desc);
  * predictors reset per interval and component); nothing outside the blocks the descriptor names is written and nothing outside
  * [scan, scan + scan_len) is read, whatever the scan or the offsets hold.  interval_offsets: n_intervals + 1 device uint64 as
  * mdct_jpegdec_index leaves them, or the row_offsets of mdct_jpeg_pack_rows / mdct_fwd_*_jpeg_scan when the producer knows them.
- * interval_status: n_intervals device uint32, MDCT_JPEGDEC_* per interval.  One launch, one workgroup per interval. */
+ * interval_status: n_intervals device uint32, MDCT_JPEGDEC_* per interval: the first error in decoding order.  One launch, one workgroup
+ * per interval.
+ * An interval that fails leaves this in its blocks: those before the failing block hold their levels, exactly; the failing block holds
+ * the levels decoded before the error (its DC only once the difference was complete) and zeros elsewhere; every block after it is zero.
+ * An interval that is UNEXPECTED_MARKER / LEFTOVER after its last block has all its blocks.  Other intervals are not
+ * touched by it.
+ * The DC predictor is a 32-bit sum of the differences; the level stored is its low 16 bits, (int16_t)pred.  T.81 keeps a conforming
+ * stream's DC within 11 bits, so a sum beyond int16 is no error class here: it wraps, and the interval's status stays what it was. */
 int mdct_jpegdec_decode(const mdct_jpegdec_scan *desc, const mdct_jpegdec_tables *tables, const uint8_t *scan, size_t scan_len,
                         const uint64_t *interval_offsets, uint32_t *interval_status, void *stream);
 

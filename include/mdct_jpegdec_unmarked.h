@@ -35,6 +35,9 @@ size_t mdct_jpegdec_unmarked_workspace(const mdct_jpegdec_scan *desc, size_t sca
  * first uint32 is the last fix round in which some chunk's state changed (0: none did).
  * status: 2 device uint32 -- [0] MDCT_JPEGDEC_*, [1] number of blocks (in decoding order) decoded before the first error (all of the
  * scan's blocks for OK / LEFTOVER / UNEXPECTED_MARKER after the last block, 0 for NOT_SYNCHRONISED).
+ * After an error at block n = status[1] the planes hold: blocks 0 .. n - 1 their levels, exactly; block n the levels decoded before the
+ * error (its DC only once the difference was complete) and zeros elsewhere; every block after n zero.  NOT_SYNCHRONISED leaves every
+ * block zero.  The DC predictor wraps as in mdct_jpegdec_decode: the level stored is (int16_t)pred.
  * sync_rounds >= 0 (4 is usually plenty). */
 int mdct_jpegdec_decode_unmarked(const mdct_jpegdec_scan *desc, const mdct_jpegdec_tables *tables, const uint8_t *scan, size_t scan_len,
                                  void *workspace, size_t workspace_bytes, uint32_t *status, int sync_rounds, void *stream);

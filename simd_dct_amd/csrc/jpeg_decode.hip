@@ -17,7 +17,8 @@
 //                      While speculating, an invalid code (skip one bit) or a run past index 63 ends the block instead of stopping
 //                      the lane: a lane that stopped would publish no usable state, and the lanes after it would become exact one
 //                      round at a time.  From its exact start the last pass meets the same symbols; there such an error is the
-//                      interval's status.
+//                      interval's status, and the blocks after the failing one are zeroed again (the lanes behind the error wrote
+//                      levels of the re-synchronised decode into them).
 // Byte unstuffing happens in the bit reader; positions a lane hands to the next are counted in bits after unstuffing from the next
 // sub-sequence's first data byte, so both lanes count the same way.  Every loop has a bound; no workgroup waits for another.
 #include <hip/hip_runtime.h>
@@ -40,7 +41,7 @@ __global__ void __launch_bounds__(kThreads) k_decode(DecArgs a)
   __shared__ uint32_t exit_state[kThreads];
   __shared__ uint32_t lcomp[16];
   __shared__ int wtot[kThreads / 64];
-  __shared__ uint32_t first_err, fin_word;
+  __shared__ uint32_t first_err, fin_word, fail_unit;
   const int tid = threadIdx.x;
   const uint32_t k = blockIdx.x;
   {
@@ -136,10 +137,11 @@ __global__ void __launch_bounds__(kThreads) k_decode(DecArgs a)
   wg_sync();
 
   // ---- the decode proper
+  Lane F;
+  F.blocks = 0;
   if (active)
   {
     reader_init(r, a, s0, e, E, tid == 0);
-    Lane F;
     run<true>(r, a, T, lcomp, my_start, F, (uint32_t)unit0, units, mcu0, pred, cap);
     if (F.err && (uint32_t)unit0 < units)
       atomicMin(&first_err, ((uint32_t)tid << 8) | F.err);
@@ -147,6 +149,25 @@ __global__ void __launch_bounds__(kThreads) k_decode(DecArgs a)
       fin_word = F.fin;
   }
   wg_sync();
+  if (first_err != kNone)
+  {
+    // The lanes after the one that met the interval's first error started from states of the speculating passes, which carry on past
+    // such an error: what they wrote lies in blocks after the failing one and means nothing.  Those blocks go back to zero; the
+    // failing block keeps the levels decoded before the error (unit0 + F.blocks < units in the lane that reported it).
+    if ((uint32_t)tid == first_err >> 8)
+      fail_unit = (uint32_t)unit0 + (uint32_t)F.blocks;
+    __threadfence();
+    wg_sync();
+    const uint32_t z0 = fail_unit + 1, nz = units - z0;
+    for (uint32_t wi = tid; wi < nz * 8; wi += kThreads)
+    {
+      const uint32_t unit = z0 + wi % nz, row = wi / nz;
+      const uint32_t mcu = mcu0 + unit / a.upm, b = unit % a.upm, c = a.bcomp[b];
+      const uint32_t my = mcu / a.mcus_x, mx = mcu - my * a.mcus_x;
+      int16_t *p = a.plane[c] + ((size_t)(my * a.cv[c] + a.bv[b]) * 8 + row) * a.pitch[c] + (size_t)(mx * a.ch[c] + a.bh[b]) * 8;
+      *(uint4 *)p = make_uint4(0, 0, 0, 0);
+    }
+  }
   if (tid == 0)
   {
     uint32_t st = first_err != kNone ? (first_err & 0xFF) : (fin_word != kNone ? fin_word : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);

@@ -24,7 +24,8 @@
 //   k_um_write   one workgroup per chunk: each lane's first block and DC predictors from the chunk's prefix and the lanes' prefix, then
 //                the exact decode of its range, writing levels, as k_decode's last pass.  The first error in decoding order, and the
 //                number of blocks before it, per chunk
-//   k_um_final   one workgroup: the scan's status and block count from the chunks' first errors
+//   k_um_final   one workgroup: the scan's status and block count from the chunks' first errors; after an error, the blocks behind the
+//                failing one zeroed again (the lanes behind the error wrote levels of the re-synchronised decode into them)
 // No workgroup waits for another inside a launch: every hand-off between chunks crosses a kernel boundary.  Every loop has a bound.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -364,9 +365,12 @@ __global__ void __launch_bounds__(kThreads) k_um_write(UmArgs a)
 
 __global__ void __launch_bounds__(1024) k_um_final(UmArgs a)
 {
-  __shared__ uint32_t first;
+  __shared__ uint32_t first, zero_from;
   if (threadIdx.x == 0)
+  {
     first = kNone;
+    zero_from = a.units;
+  }
   __syncthreads();
   if (!a.ctl[kSyncOk])
   {
@@ -394,6 +398,7 @@ __global__ void __launch_bounds__(1024) k_um_final(UmArgs a)
     {
       st = a.cerr[first] & 0xFF;
       n = a.ccnt[first];
+      zero_from = n + 1;
     }
     else if (a.ctl[kFin] != kNone)
     {
@@ -407,6 +412,19 @@ __global__ void __launch_bounds__(1024) k_um_final(UmArgs a)
     }
     a.status[0] = st;
     a.status[1] = n;
+  }
+  __syncthreads();
+  // After an error the lanes and chunks behind it wrote levels of the re-synchronised decode into blocks after the failing one (block n):
+  // those go back to zero.  Block n keeps the levels decoded before the error.  An error path only: one workgroup is enough.
+  const uint32_t z0 = zero_from < a.units ? zero_from : a.units;
+  const uint64_t nz = a.units - z0;
+  for (uint64_t wi = threadIdx.x; wi < nz * 8; wi += 1024)
+  {
+    const uint32_t row = (uint32_t)(wi / nz), unit = z0 + (uint32_t)(wi - (uint64_t)row * nz);
+    const uint32_t mcu = unit / a.d.upm, b = unit - mcu * a.d.upm, c = a.d.bcomp[b];
+    const uint32_t my = mcu / a.d.mcus_x, mx = mcu - my * a.d.mcus_x;
+    int16_t *p = a.d.plane[c] + ((size_t)(my * a.d.cv[c] + a.d.bv[b]) * 8 + row) * a.d.pitch[c] + (size_t)(mx * a.d.ch[c] + a.d.bh[b]) * 8;
+    *(uint4 *)p = make_uint4(0, 0, 0, 0);
   }
 }
 

@@ -163,6 +163,8 @@ def read_jpeg(data, require_restart=True):
         if m in (0xC0, 0xC1):
             if frame is not None:
                 raise JpegFormatError("a second frame header")
+            if len(seg) < 6:
+                raise JpegFormatError("malformed frame header")
             P, Y, X, nf = struct.unpack_from(">BHHB", seg)
             if P != 8:
                 raise JpegFormatError(f"not supported: {P}-bit samples (8-bit only)")
@@ -213,7 +215,7 @@ def read_jpeg(data, require_restart=True):
         elif m == 0xDA:
             if frame is None:
                 raise JpegFormatError("SOS before the frame header")
-            ns = seg[0]
+            ns = seg[0] if seg else 0
             if ns < 1 or ns > 3 or len(seg) != 4 + 2 * ns:
                 raise JpegFormatError("malformed SOS")
             ids = [c["id"] for c in frame["components"]]

@@ -155,6 +155,40 @@ def scan_geometry(info, scan, geo, grid):
     return grid[0], grid[1], [(c["index"], comps[c["index"]]["h"], comps[c["index"]]["v"]) for c in scan["components"]]
 
 
+def scan_plan(info, si, sc, geo, grid, coefs):
+    """Everything decode_jpeg settles about scan si on the host before its first launch: the Huffman specifications the scan names
+    (JpegFormatError for one that is not defined), their validation (tables_check) and the descriptor over the coefficient planes,
+    which the library it goes to must accept (MdctError).  coefs: one int16 tensor per component, [rows, blocks_x * 8].
+    -> (specs, desc)"""
+    mcus_x, mcus_y, members = scan_geometry(info, sc, geo, grid)
+    specs = [None] * 4
+    planes = []
+    for c, (ci, h, v) in zip(sc["components"], members):
+        for slot, key in ((c["td"], (0, c["td"])), (2 + c["ta"], (1, c["ta"]))):
+            if key not in sc["huffman"]:
+                raise jfif.JpegFormatError(f"scan {si} uses Huffman table {key} that is not defined")
+            specs[slot] = sc["huffman"][key]
+        planes.append((coefs[ci], geo[ci][2], geo[ci][3], h, v, c["td"], 2 + c["ta"]))
+    if tables_check(specs) != 0:
+        raise api.MdctError(f"scan {si}: {last_error()}")
+    desc = scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"])
+    if sc["restart_interval"]:
+        n_intervals(desc)
+    elif unmarked_workspace(desc, sc["end"] - sc["start"]) == 0:
+        raise api.MdctError(f"invalid scan descriptor: {unmarked_last_error()}")
+    return specs, desc
+
+
+def component_luts(info):
+    """the quantisation table of every component as float32 [64]; JpegFormatError for one that is not defined"""
+    luts = []
+    for c in info["components"]:
+        if c["tq"] not in info["qtables"]:
+            raise jfif.JpegFormatError(f"quantisation table {c['tq']} is not defined")
+        luts.append(info["qtables"][c["tq"]].astype(np.float32))
+    return luts
+
+
 SCALE_DENOMS = (1, 2, 4, 8)
 
 
@@ -237,11 +271,7 @@ def scaled_planes(info, coefs, scale_denom, stream=None, replicate=False):
     geo, _ = geometry(info)
     sgeo, (sw, sh) = scaled_geometry(info, scale_denom)
     reps = colour_sampling(info, scale_denom)[1] if replicate else [(1, 1)] * len(sgeo)
-    luts = []
-    for c in info["components"]:
-        if c["tq"] not in info["qtables"]:
-            raise jfif.JpegFormatError(f"quantisation table {c['tq']} is not defined")
-        luts.append(info["qtables"][c["tq"]].astype(np.float32))
+    luts = component_luts(info)
     px = [torch.empty((g[3] * sg[0] * r[1], g[2] * sg[0] * r[0]), dtype=torch.uint8, device=q.device) for g, sg, q, r in zip(geo, sgeo, coefs, reps)]
     full = [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, sg, lut in zip(px, coefs, geo, sgeo, luts) if sg[0] == 8]
     small = [(p, q, g[2], g[3], lut, sg[0], r) for p, q, g, sg, lut, r in zip(px, coefs, geo, sgeo, luts, reps) if sg[0] != 8]
@@ -283,17 +313,8 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
     coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
     with torch.cuda.device(dev):
         for si, sc in enumerate(info["scans"]):
-            mcus_x, mcus_y, members = scan_geometry(info, sc, geo, grid)
-            specs = [None] * 4
-            planes = []
-            for c, (ci, h, v) in zip(sc["components"], members):
-                for slot, key in ((c["td"], (0, c["td"])), (2 + c["ta"], (1, c["ta"]))):
-                    if key not in sc["huffman"]:
-                        raise jfif.JpegFormatError(f"scan {si} uses Huffman table {key} that is not defined")
-                    specs[slot] = sc["huffman"][key]
-                planes.append((coefs[ci], geo[ci][2], geo[ci][3], h, v, c["td"], 2 + c["ta"]))
+            specs, desc = scan_plan(info, si, sc, geo, grid, coefs)
             tables = Tables(specs)
-            desc = scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"])
             seg = torch.frombuffer(bytearray(raw[sc["start"]:sc["end"]]) or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
             L = sc["end"] - sc["start"]
             if sc["restart_interval"] == 0:
@@ -322,11 +343,7 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
                 out = to_rgb(out, colour_sampling(info, scale_denom)[0], sw, sh, colour=info["colorspace"], layout=layout, stream=stream)
             return (out, coefs) if coefficients else out
         px = [torch.empty((by * 8, bx * 8), dtype=torch.uint8, device=dev) for _, _, bx, by in geo]
-        luts = []
-        for c in info["components"]:
-            if c["tq"] not in info["qtables"]:
-                raise jfif.JpegFormatError(f"quantisation table {c['tq']} is not defined")
-            luts.append(info["qtables"][c["tq"]].astype(np.float32))
+        luts = component_luts(info)
         api.u8_i16_batch("inv", [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, lut in zip(px, coefs, geo, luts)], level_shift=True, stream=stream)
         out = [p[:g[1], :g[0]] for p, g in zip(px, geo)]
         if mode == "RGB":

@@ -149,11 +149,14 @@ def extend(v, s):
     return v - (1 << s) + 1 if s and v < (1 << (s - 1)) else v
 
 
-def decode_block(rd, dc_table, ac_table):
-    """F.2.2.1 / F.2.2.2 -> (DC difference, {zig-zag index: level})"""
+def decode_block(rd, dc_table, ac_table, seen=None):
+    """F.2.2.1 / F.2.2.2 -> (DC difference, {zig-zag index: level}).  seen: a dict that receives what has been decoded of the block as
+    it goes ("dc": the difference, zig-zag index: level), so that a caller still has it when the block fails."""
     s = rd.decode(dc_table)
     diff = extend(rd.receive(s), s)
-    ac, k = {}, 1
+    ac, k = ({} if seen is None else seen), 1
+    if seen is not None:
+        seen["dc"] = diff
     while k < 64:
         rs = rd.decode(ac_table)
         r, s = rs >> 4, rs & 15
@@ -169,30 +172,52 @@ def decode_block(rd, dc_table, ac_table):
             raise _Fail(COEF_OVERFLOW)
         ac[k] = extend(rd.receive(s), s)
         k += 1
-    return diff, ac
+    return diff, {k: v for k, v in ac.items() if k != "dc"}
 
 
-def decode_interval(data, units, tables, marker_after):
-    """one restart interval: units = [(component, dc table, ac table, place)] in decoding order -> (status, [(place, 64 levels natural)])"""
+def decode_interval(data, units, tables, marker_after, partial=False):
+    """one restart interval: units = [(component, dc table, ac table, place)] in decoding order -> (status, [(place, 64 levels natural)]).
+    partial=True -> (status, blocks, failing, n): failing = (place, 64 levels natural) of the block the decoder was in when it failed,
+    holding what had been decoded of it (the DC only once its difference was complete; None when no block failed), n = the number of
+    complete blocks before it."""
     rd = _Bits(data)
     pred, out = {}, []
+    failing = None
+    status = None
     try:
         for comp, dct, act, place in units:
-            diff, ac = decode_block(rd, tables[dct], tables[act])
+            seen = {}
+            failing = (comp, place, seen)
+            diff, ac = decode_block(rd, tables[dct], tables[act], seen)
             pred[comp] = pred.get(comp, 0) + diff
             blk = np.zeros(64, dtype=np.int64)
             blk[0] = pred[comp]
             for k, v in ac.items():
                 blk[ZIGZAG[k]] = v
             out.append((place, blk))
+            failing = None
     except _Fail as f:
-        return f.status, out
-    rem = rd.bits[rd.pos:]
-    if len(rem) >= 8 or not all(rem):
-        return LEFTOVER, out
-    if rd.marker:
-        return UNEXPECTED_MARKER, out
-    return (OK if marker_after is None or marker_after[0] else UNEXPECTED_MARKER), out
+        status = f.status
+    if status is None:
+        rem = rd.bits[rd.pos:]
+        if len(rem) >= 8 or not all(rem):
+            status = LEFTOVER
+        elif rd.marker:
+            status = UNEXPECTED_MARKER
+        else:
+            status = OK if marker_after is None or marker_after[0] else UNEXPECTED_MARKER
+    if not partial:
+        return status, out
+    if failing is not None:
+        comp, place, seen = failing
+        blk = np.zeros(64, dtype=np.int64)
+        if "dc" in seen:
+            blk[0] = pred.get(comp, 0) + seen["dc"]
+        for k, v in seen.items():
+            if k != "dc":
+                blk[ZIGZAG[k]] = v
+        failing = (place, blk)
+    return status, out, failing, len(out)
 
 
 def decode(data, intervals=None):

@@ -111,12 +111,52 @@ def _new_stats():
                 stuffed=[], markers=[], intervals=[], pad_bits=[], length=0)
 
 
-def encode_scan(frame, scan, planes, specs):
+def _put_items(w, items, dct, act):
+    """write injected items: a str of '0' / '1' is raw bits; (table class 0 DC / 1 AC, symbol, extra, n_extra) is that symbol's code in
+    the block's table followed by n_extra bits of extra"""
+    for it in items:
+        if isinstance(it, str):
+            for ch in it:
+                w.put(int(ch), 1)
+        else:
+            cls, sym, extra, n_extra = it
+            code, n = (act if cls else dct)[sym]
+            w.put(code, n)
+            w.put(extra & ((1 << n_extra) - 1), n_extra)
+
+
+def stuffed_offset(st, k, bit):
+    """scan offset of the stuffed byte that holds bit `bit` (counted after unstuffing) of interval k's data, from encode_scan's stats
+    (of a scan without spliced bytes before that bit)"""
+    base = st["intervals"][k][0]
+    o = base + bit // 8
+    for f in st["stuffed"]:
+        if base <= f < o:
+            o += 1
+    return o
+
+
+def encode_scan(frame, scan, planes, specs, inject=None):
     """-> (entropy-coded bytes, stuffed and with RSTm markers; stats).  stats: lengths {(class, id): Counter(code length)} over every
     coded symbol, dc_categories / dc_diffs, ac_symbols (Counter of RS), ac_values, zrl_chains (Counter: ZRLs before a level), blocks,
     zero_blocks, ends_at_63 (blocks whose last level is at index 63: no EOB), max_block_bits, stuffed (offsets of the 0xFF of every
     stuffed pair), markers (offsets of every RSTm's 0xFF), intervals ([start, end) of each interval's data), pad_bits (per interval),
-    length."""
+    length.
+
+    inject (optional; without it the scan is what the planes say): a dict that writes something wrong at a chosen place.  Its keys:
+      block, at, put[, drop_rest]: in block `block` (decoding order over the scan) the symbol at `at` -- "dc", or n for the n-th AC
+        symbol the block would have (ZRLs, levels with their extra bits and the EOB each count as one) -- is replaced by the items of
+        `put` (see _put_items; [] drops the symbol).  With drop_rest the block's remaining symbols are not written either.
+      append: {interval: items} written after the interval's last block, before its padding.
+      stop: (interval, bits, pad): the interval's bit stream is cut after `bits` bits; pad=True fills the last byte with 1-bits,
+        pad=False drops a partial last byte.
+      splice: (interval, bits, raw bytes): the bytes go into the interval's stuffed data, not stuffed themselves, in front of the byte
+        that holds bit `bits` (a multiple of 8; the interval's length in bits or more: after its last byte).
+      trace: True -> stats["symbols"] = per interval [(block, at, first bit, code bits, extra bits)] of every true symbol written.
+    stats then also hold inject_interval, inject_bit / inject_end_bit (the first bit of the items of `put` and the bit after the
+    last, counted in the interval's data after unstuffing), inject_offset / inject_end_offset (scan offsets of the stuffed bytes that
+    hold the first and the last of those bits), stop_offset / splice_offset (scan offset where the data was cut / the bytes begin)."""
+    inj = inject or {}
     order, n_mcus, upm = block_order(frame, scan)
     dri = scan.get("dri", 0) or n_mcus
     fill = scan.get("fill", {})
@@ -131,7 +171,17 @@ def encode_scan(frame, scan, planes, specs):
         rows, cols = p.shape[0] // 8, p.shape[1] // 8
         zz_planes[ci] = p.reshape(rows, 8, cols, 8).transpose(0, 2, 1, 3).reshape(rows, cols, 64)[:, :, ZZ]
     n_int = -(-n_mcus // dri)
+    if inj.get("trace"):
+        st["symbols"] = [[] for _ in range(n_int)]
     for k in range(n_int):
+        if inj:
+            body, pad = _encode_interval_injected(k, order[k * dri * upm:min((k + 1) * dri, n_mcus) * upm], k * dri * upm, tabs, zz_planes, st, inj)
+            _emit_interval(out, st, body, pad, k, inj)
+            if k + 1 < n_int:
+                out += b"\xff" * fill.get(k, 0)
+                st["markers"].append(len(out))
+                out += bytes([0xFF, 0xD0 + (k & 7)])
+            continue
         w = _Writer()
         pred = {}
         for ci, by, bx in order[k * dri * upm:min((k + 1) * dri, n_mcus) * upm]:
@@ -200,6 +250,90 @@ def encode_scan(frame, scan, planes, specs):
     return bytes(out), st
 
 
+def _encode_interval_injected(k, blocks, first_block, tabs, zz_planes, st, inj):
+    """one interval's unstuffed bytes with the injection applied: the same symbols as encode_scan's own loop, listed first, then
+    written one at a time so that one of them can be replaced.  Of the statistics only blocks, the trace and the injection's are kept."""
+    w = _Writer()
+    pred = {}
+    now = lambda: len(w.out) * 8 + w.n  # noqa: E731
+    for bi, (ci, by, bx) in enumerate(blocks, first_block):
+        dck, dct, ack, act = tabs[ci]
+        z = zz_planes[ci][by, bx]
+        diff = int(z[0]) - pred.get(ci, 0)
+        pred[ci] = int(z[0])
+        s = category(diff)
+        if s > 11:
+            raise ValueError(f"DC difference {diff} beyond category 11")
+        syms = [("dc", 0, s, diff if diff >= 0 else diff + (1 << s) - 1, s)]
+        k0, n = 1, 0
+        for pos in (np.flatnonzero(z[1:]) + 1).tolist():
+            v, r = int(z[pos]), pos - k0
+            while r > 15:
+                syms.append((n, 1, 0xF0, 0, 0))
+                n += 1
+                r -= 16
+            s = category(v)
+            if s > 10:
+                raise ValueError(f"AC level {v} beyond size 10")
+            syms.append((n, 1, (r << 4) | s, v if v >= 0 else v + (1 << s) - 1, s))
+            n += 1
+            k0 = pos + 1
+        if k0 < 64:
+            syms.append((n, 1, 0x00, 0, 0))
+        for at, cls, sym, extra, n_extra in syms:
+            if inj.get("block") == bi and inj.get("at") == at:
+                st["inject_interval"], st["inject_bit"] = k, now()
+                _put_items(w, inj["put"], dct, act)
+                st["inject_end_bit"] = now()
+                if inj.get("drop_rest"):
+                    break
+                continue
+            if "symbols" in st:
+                st["symbols"][k].append((bi, at, now(), (act if cls else dct)[sym][1], n_extra))
+            _put_items(w, [(cls, sym, extra, n_extra)], dct, act)
+        st["blocks"] += 1
+    if k in inj.get("append", {}):
+        ci = blocks[-1][0]
+        _put_items(w, inj["append"][k], tabs[ci][1], tabs[ci][3])
+    st["interval_bits"] = st.get("interval_bits", []) + [now()]
+    return w.finish()
+
+
+def _emit_interval(out, st, data, pad, k, inj):
+    """stuff one interval's bytes and append them to out, cut (stop) or with raw bytes spliced in (splice) as the injection says"""
+    if inj.get("stop") and inj["stop"][0] == k:
+        _, bits, padded = inj["stop"]
+        nbytes, rem = bits // 8, bits % 8
+        if rem and padded:
+            data = data[:nbytes] + bytes([data[nbytes] | (0xFF >> rem)])
+        else:
+            data = data[:nbytes]
+        pad = (8 - rem) % 8 if padded else 0
+    a = np.frombuffer(data, dtype=np.uint8)
+    ff = np.flatnonzero(a == 0xFF)
+    base = len(out)
+    stuffed = (base + ff + np.arange(ff.size)).tolist()
+    body = np.insert(a, ff + 1, 0).tobytes() if ff.size else bytes(data)
+    if inj.get("stop") and inj["stop"][0] == k:
+        st["stop_offset"] = base + len(body)
+    if inj.get("splice") and inj["splice"][0] == k:
+        _, bits, raw = inj["splice"]
+        if bits % 8:
+            raise ValueError("bytes are spliced in at a byte boundary")
+        j = min(bits // 8, len(a))
+        at = j + int((ff < j).sum())
+        body = body[:at] + bytes(raw) + body[at:]
+        stuffed = [f if f < base + at else f + len(raw) for f in stuffed]
+        st["splice_offset"] = base + at
+    st["stuffed"] += stuffed
+    out += body
+    st["intervals"].append((base, len(out)))
+    st["pad_bits"].append(pad)
+    if st.get("inject_interval") == k and "inject_offset" not in st:
+        st["inject_offset"] = stuffed_offset(st, k, st["inject_bit"])
+        st["inject_end_offset"] = stuffed_offset(st, k, max(st["inject_bit"], st["inject_end_bit"] - 1))
+
+
 def _seg(marker, payload):
     return bytes([0xFF, marker]) + struct.pack(">H", len(payload) + 2) + payload
 
@@ -219,10 +353,10 @@ ANNEX_K = {
 }
 
 
-def encode_file(frame, scans, planes, specs, qtables=None, table_per_component=False):
+def encode_file(frame, scans, planes, specs, qtables=None, table_per_component=False, inject=None):
     """-> (a complete JFIF file, [stats of each scan, with 'start': the scan's first byte in the file]).  qtables: [64] natural order per
     component (default: 1 for the first component, 2 for the others); components take quantisation table 0 (first) / 1 (others), or
-    with table_per_component table ci each (up to 4 components, T.81 B.2.4.1)."""
+    with table_per_component table ci each (up to 4 components, T.81 B.2.4.1).  inject: {scan index: encode_scan's inject}."""
     nc = len(frame["comps"])
     if qtables is None:
         qtables = [np.ones(64, dtype=np.uint16)] + [np.full(64, 2, dtype=np.uint16)] * (nc - 1)
@@ -237,12 +371,12 @@ def encode_file(frame, scans, planes, specs, qtables=None, table_per_component=F
     f.append(_seg(0xC0, sof))
     f.append(_seg(0xC4, b"".join(bytes([(tc << 4) | th]) + bytes(b) + bytes(v) for (tc, th), (b, v) in sorted(specs.items()))))
     stats, dri = [], None
-    for sc in scans:
+    for si, sc in enumerate(scans):
         if sc.get("dri", 0) != dri:
             dri = sc.get("dri", 0)
             f.append(_seg(0xDD, struct.pack(">H", dri)))
         f.append(_seg(0xDA, bytes([len(sc["comps"])]) + b"".join(bytes([ci + 1, (td << 4) | ta]) for ci, td, ta in sc["comps"]) + b"\x00\x3f\x00"))
-        body, st = encode_scan(frame, sc, planes, specs)
+        body, st = encode_scan(frame, sc, planes, specs, inject=(inject or {}).get(si))
         st["start"] = sum(map(len, f))
         f.append(body + b"\xff" * sc.get("fill_end", 0))
         stats.append(st)
