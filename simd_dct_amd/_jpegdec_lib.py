@@ -53,15 +53,7 @@ _lib_handle = None
 def load():
     """Load libmdct_jpegdec.so (once), after libmdct_hip.so (whose launch tally and HIP runtime it shares)."""
     global _lib_handle
-    if _lib_handle is not None:
-        return _lib_handle
-    _lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
-    lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib_handle = lib
-    return lib
+    if _lib_handle is None:
+        _lib.load()
+        _lib_handle = _lib.bind(LIB_PATH, SIGNATURES)
+    return _lib_handle

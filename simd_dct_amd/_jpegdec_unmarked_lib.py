@@ -7,7 +7,7 @@ libmdct_hip.so.  No fallback: if the shared object is missing or fails to load, 
 import ctypes
 import os
 
-from . import _jpegdec_lib
+from . import _jpegdec_lib, _lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmdct_jpegdec_unmarked.so")
@@ -34,15 +34,7 @@ _lib_handle = None
 def load():
     """Load libmdct_jpegdec_unmarked.so (once), after libmdct_jpegdec.so and libmdct_hip.so."""
     global _lib_handle
-    if _lib_handle is not None:
-        return _lib_handle
-    _jpegdec_lib.load()
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
-    lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib_handle = lib
-    return lib
+    if _lib_handle is None:
+        _jpegdec_lib.load()
+        _lib_handle = _lib.bind(LIB_PATH, SIGNATURES)
+    return _lib_handle

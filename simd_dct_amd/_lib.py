@@ -140,26 +140,28 @@ MANGLED = (
 _lib = None
 
 
+def bind(path, signatures, hint=""):
+    """Load the shared object at `path` and declare restype / argtypes of every function in `signatures`."""
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).{hint}")
+    lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load():
     """Load libmdct_hip.so (once).  torch is imported first when available so that the
     library binds to the SAME libamdhip64 the process's tensors live in."""
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  simd_dct_amd has no CPU fallback."
-        )
-    if os.environ.get("MDCT_NO_TORCH_PRELOAD") != "1":  # host-only users (e.g. the CPU multi-rank test's children) skip the import
+    if os.path.exists(LIB_PATH) and os.environ.get("MDCT_NO_TORCH_PRELOAD") != "1":  # host-only users (e.g. the CPU multi-rank test's children) skip the import
         try:
             import torch  # noqa: F401  (side effect: loads torch's HIP runtime before ours resolves)
         except Exception:
             pass
-    lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    _lib = bind(LIB_PATH, SIGNATURES, "  simd_dct_amd has no CPU fallback.")
+    return _lib

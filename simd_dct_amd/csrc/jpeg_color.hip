@@ -15,26 +15,11 @@
 // row's end and every pixel of kAny go through sample(): one pixel at a time, with byte loads and stores.  sample() is the rule itself;
 // the vector paths are its specialisation, and the tests hold both against the same checker.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "host_error.h"
 #include "launch_tally.h"
 #include "mdct_jpegcolor.h"
-
-namespace
-{
-char g_err[512];
-
-int fail(int code, const char *fmt, ...)
-{
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-} // namespace
 
 namespace mdct
 {

@@ -6,11 +6,10 @@
 // coefficients are the engine's own: the forward passes, the quantiser and the zig-zag compaction are compiled from mdct_kernels.hip's
 // MDCT_AAN_FWD_ONLY region and the multiplier tables come from own_tables.h; the bits are written by HuffSeqCoder16 (huffman_rows.h).
 //
-// One kernel template, k_opt<H, V, STATS>, in the shape of k_scan_rows (jpeg_encode_scan.hip): one workgroup per restart interval, the
-// interval worked through in chunks, a chunk in two phases separated by a barrier --
-//   transform  lane = block, component-uniform waves (wave-uniform multipliers from the argument segment); every lane leaves its
-//              block's AC entries in its LDS row and (DC, entry count, EOB flag) in meta[];
-//   symbols    thread s takes the s-th block of the chunk in scan order; its DC predictor is a plain LDS read.
+// One kernel template, k_opt<H, V, STATS>, on the chunk skeleton it shares with k_scan_rows (scan_chunks.h; layouts and scan order:
+// scan_order.h): one workgroup per restart interval, the interval worked through in chunks, a chunk in a transform phase and a symbols
+// phase separated by a barrier.  This kernel's own are the LDS, the table / ring / histogram set-up, the symbols phase and the
+// epilogue.  The host checks it shares with jpeg_encode_scan.hip are scan_host.h's.
 // <H, V> is the luma sampling of an interleaved scan (<2, 2>, <2, 1>, <1, 1>; 3 / 2 / 3 waves) or <0, 0>: ONE plane, interval = one block
 // row, 4 waves, chunks of 256 blocks, scan order = lane order.
 // STATS = false: the symbols phase is HuffSeqCoder16 with the caller's tables.  Unless the host found the tables complete, a walk
@@ -20,35 +19,20 @@
 //   of up to 64 serialised atomics -- and added to the caller's histogram once per workgroup with vector atomics.  Integer sums: the
 //   result does not depend on the order.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "aan_fwd.h"
 #define MDCT_AAN_FWD_ONLY
 #include "mdct_kernels.hip" // only its MDCT_AAN_FWD_ONLY region: aan_fwd_h, aan_fwd_v, fwd_v_quant_levels, compact_levels16
-#include "huffman_rows.h"
+#include "host_error.h"
 #include "launch_tally.h"
 #include "mdct_jpegenc_opt.h"
-#include "own_tables.h"
+#include "scan_chunks.h"
+#include "scan_host.h"
 #include "wg_sync.h"
 
 #pragma clang fp contract(off)
-
-namespace
-{
-char g_err[512];
-
-int fail(int code, const char *fmt, ...)
-{
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-} // namespace
 
 namespace mdct
 {
@@ -79,66 +63,7 @@ struct OptArgs
 };
 static_assert(sizeof(OptArgs) <= 4096, "kernel argument block");
 
-template <int H, int V> constexpr int kBlocksPerMcu = H == 0 ? 1 : H * V + 2;
-template <int H, int V> constexpr int kWaves = H == 0 ? 4 : H == 2 ? V + 1 : 3;              // one plane 4, 4:2:0 3, 4:2:2 2, 4:4:4 3
-template <int H, int V> constexpr uint32_t kMcus = H == 0 ? 256u : H == 2 ? 32u : 64u;       // MCUs per chunk: 64 * kWaves blocks
-
-// where the s-th block of a chunk in scan order was transformed (slot = wave * 64 + lane), where its predecessor of the same component
-// was (pred; carry: it is the component's last block of the previous chunk), and whether it is a chroma block (k_scan_rows' seq_block)
-struct SeqBlock
-{
-  uint32_t mcu, slot, pred;
-  bool carry, chroma;
-};
-
-template <int H, int V>
-__device__ __forceinline__ SeqBlock seq_block(uint32_t s)
-{
-  constexpr uint32_t B = kBlocksPerMcu<H, V>, M = kMcus<H, V>;
-  const uint32_t i = s / B, k = s - i * B;
-  SeqBlock b;
-  b.mcu = i;
-  if constexpr (H == 0)
-  { // one plane: lane order
-    b.chroma = false;
-    b.slot = s;
-    b.carry = s == 0;
-    b.pred = b.carry ? M - 1 : s - 1;
-  }
-  else if constexpr (H == 1)
-  { // Y Cb Cr: wave k, lane i
-    b.chroma = k > 0;
-    b.slot = k * 64 + i;
-    b.carry = i == 0;
-    b.pred = b.carry ? k * 64 + 63 : b.slot - 1;
-  }
-  else
-  {
-    constexpr uint32_t NY = H * V, C0 = 64 * V; // luma blocks per MCU, the chroma wave's first slot
-    b.chroma = k >= NY;
-    if (k >= NY)
-    { // Cb: lanes 0..31 of the chroma wave, Cr: lanes 32..63
-      const uint32_t first = C0 + (k - NY) * M;
-      b.slot = first + i;
-      b.carry = i == 0;
-      b.pred = b.carry ? first + M - 1 : b.slot - 1;
-    }
-    else if constexpr (V == 1)
-    { // Y0 Y1: lanes 2i, 2i + 1 of wave 0
-      b.slot = 2 * i + k;
-      b.carry = b.slot == 0;
-      b.pred = b.carry ? 63 : b.slot - 1;
-    }
-    else
-    { // Y00 Y01 Y10 Y11: wave k >> 1 (the luma block row), lane 2i + (k & 1)
-      b.slot = (k >> 1) * 64 + 2 * i + (k & 1);
-      b.carry = s == 0;
-      // Y00 follows the previous MCU's Y11, Y01 Y00, Y10 Y01, Y11 Y10
-      b.pred = k == 0 ? (b.carry ? 127 : 64 + 2 * i - 1) : k == 1 ? 2 * i : k == 2 ? 2 * i + 1 : 64 + 2 * i;
-    }
-  }
-  return b;
-}
+using namespace scan_order;
 
 // SSSS of a DC difference as huff_dc_token codes it
 __device__ __forceinline__ uint32_t dc_category(int diff)
@@ -162,12 +87,12 @@ __device__ __forceinline__ uint32_t ac_symbol12(uint32_t e)
 template <int H, int V, bool STATS>
 __global__ __launch_bounds__((64 * kWaves<H, V>)) void k_opt(OptArgs a)
 {
+  using Chunks = ScanChunks<H, V, OptArgs>;
   constexpr int WAVES = kWaves<H, V>;
-  constexpr uint32_t kThreads = 64 * WAVES, M = kMcus<H, V>;
-  static_assert(kThreads == M * kBlocksPerMcu<H, V>, "one symbols thread per block of the chunk");
+  constexpr uint32_t kThreads = Chunks::kThreads, M = Chunks::M;
   __shared__ uint32_t ac[STATS ? 1 : 2][256], dc[STATS ? 1 : 2][12];
   __shared__ __attribute__((aligned(16))) uint16_t rec_all[kThreads * kRec16Row];
-  __shared__ uint32_t meta[2][kThreads]; // DC (low 16 bits) | entries << 16 | EOB needed << 24, by slot; [chunk parity]
+  __shared__ uint32_t meta[2][kThreads]; // by slot; [chunk parity] (ScanChunks)
   __shared__ uint32_t ring[STATS ? 1 : kRing];
   __shared__ uint32_t tot[2][WAVES];
   __shared__ uint32_t ff_total;
@@ -195,58 +120,8 @@ __global__ __launch_bounds__((64 * kWaves<H, V>)) void k_opt(OptArgs a)
     coder.tot = tot;
     coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)my * a.seg_stride);
   }
-  const DctConsts &C = a.consts;
-  const AanPk &K = reinterpret_cast<const AanPk &>(C);
-
-  // ---- the transform phase's block of this thread: plane, block row, first block and blocks per chunk
-  const bool chroma_wave = H == 0 ? false : H == 1 ? wave > 0 : wave == (uint32_t)V;
-  uint32_t comp, bx0, step, last_blk, brow;
-  if (H == 0)
-  {
-    comp = 0;
-    bx0 = tid;
-    step = 256;
-    last_blk = a.mcus_x - 1;
-    brow = my;
-  }
-  else if (H == 1)
-  {
-    comp = wave;
-    bx0 = lane;
-    step = 64;
-    last_blk = a.mcus_x - 1;
-    brow = my;
-  }
-  else if (!chroma_wave)
-  {
-    comp = 0;
-    bx0 = lane;
-    step = 64;
-    last_blk = 2 * a.mcus_x - 1;
-    brow = my * V + wave;
-  }
-  else
-  {
-    comp = 1 + (lane >> 5);
-    bx0 = lane & 31;
-    step = 32;
-    last_blk = a.mcus_x - 1;
-    brow = my;
-  }
-  // (selects, not an index: the argument block stays in scalar registers)
-  const size_t pitch = comp == 0 ? a.pitch[0] : comp == 1 ? a.pitch[1] : a.pitch[2];
-  const uint8_t *src_row = (comp == 0 ? a.px[0] : comp == 1 ? a.px[1] : a.px[2]) + (size_t)brow * 8 * pitch;
-  uint2 rows[8];
-  auto fetch = [&](uint32_t bx) { // the 8 rows of block min(bx, last) of the block row (lanes past the row's end redo the last block)
-    const uint8_t *src = src_row + (size_t)min(bx, last_blk) * 8;
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-      rows[r] = load8(src + (size_t)r * pitch);
-  };
-  fetch(bx0);
-  // the multiplier pairs of this wave's table (wave-uniform: scalar loads from the argument segment)
-  const karg_pairs_t qf = karg_pairs(offsetof(OptArgs, tb) + (chroma_wave ? sizeof(OwnTables) : 0) + offsetof(OwnTables, qf));
-  uint16_t *rec = rec_all + tid * kRec16Row;
+  Chunks chunks(a);
+  chunks.init(tid, lane, wave, my, rec_all, meta);
 
   // ---- the symbols phase's block of this thread
   const SeqBlock sb = seq_block<H, V>(tid);
@@ -259,30 +134,11 @@ __global__ __launch_bounds__((64 * kWaves<H, V>)) void k_opt(OptArgs a)
   wg_sync(); // tables and the cleared ring / histograms
   for (uint32_t m0 = 0, chunk = 0; m0 < a.mcus_x; m0 += M, chunk++)
   {
-    f32x2 P[4][8];
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-    {
-      const f32x2 a01 = f32x2{ubyte_to_float<0>(rows[r].x), ubyte_to_float<1>(rows[r].x)};
-      const f32x2 a23 = f32x2{ubyte_to_float<2>(rows[r].x), ubyte_to_float<3>(rows[r].x)};
-      const f32x2 a45 = f32x2{ubyte_to_float<0>(rows[r].y), ubyte_to_float<1>(rows[r].y)};
-      const f32x2 a67 = f32x2{ubyte_to_float<2>(rows[r].y), ubyte_to_float<3>(rows[r].y)};
-      aan_fwd_h(K, a01, a23, a45, a67, P[0][r], P[1][r], P[2][r], P[3][r]);
-    }
-    uint32_t val[64];
-    fwd_v_quant_levels<true>(K, P, qf, a.dc_shift, val);
-    int my_dc;
-    bool need_eob;
-    const uint32_t n = compact_levels16(val, rec, my_dc, need_eob);
-    meta[par][tid] = ((uint32_t)my_dc & 0xFFFFu) | n << 16 | (need_eob ? 1u << 24 : 0u);
-    if (m0 + M < a.mcus_x)
-      fetch(bx0 + (chunk + 1) * step); // in flight during the symbols phase
+    chunks.transform(m0, chunk, par);
     wg_sync(); // every block of the chunk is in LDS
-    const uint32_t me = meta[par][sb.slot];
-    const int blk_dc = (int)(int16_t)(me & 0xFFFFu);
-    const int pred = sb.carry ? (m0 == 0 ? 0 : (int)(int16_t)(meta[par ^ 1][sb.pred] & 0xFFFFu)) : (int)(int16_t)(meta[par][sb.pred] & 0xFFFFu);
-    const bool live = m0 + sb.mcu < a.mcus_x, blk_eob = (me >> 24) != 0;
-    const int blk_n = live ? (int)((me >> 16) & 0xFFu) : 0;
+    const ChunkBlock b = chunks.block(sb, m0, par);
+    const bool live = b.live, blk_eob = b.eob;
+    const int blk_dc = b.dc, pred = b.pred, blk_n = live ? b.n : 0;
     if constexpr (STATS)
     {
       uint32_t *h = whist + (cls ? kClass : 0u);
@@ -380,23 +236,25 @@ int spec_codes(const mdct_jpegenc_opt_spec *sp, bool is_ac, const char *name, ui
   if (total != sp->nvals)
     return fail(MDCT_INVALID_PARAMETER, "%s: the 16 counts add up to %d codes, %d values given", name, total, sp->nvals);
   uint32_t code = 0;
-  int p = 0;
-  for (uint32_t l = 1; l <= 16; l++)
+  bool seen[256] = {false};
+  for (uint32_t l = 1, p = 0; l <= 16; l++)
   {
-    const int n = sp->bits16[l - 1];
-    for (int i = 0; i < n; i++, p++, code++)
+    const uint32_t n = sp->bits16[l - 1];
+    for (uint32_t i = 0; i < n; i++, p++)
     {
       const int v = sp->vals[p];
       if (is_ac ? (v & 15) > 10 : v > 11)
         return fail(MDCT_INVALID_PARAMETER, "%s: value 0x%02x is not a baseline %s symbol", name, v, is_ac ? "AC" : "DC");
-      if (tab[v])
+      if (seen[v])
         return fail(MDCT_INVALID_PARAMETER, "%s: value 0x%02x is named twice", name, v);
-      tab[v] = l << 16 | code;
+      seen[v] = true;
     }
+    code += n;
     if (code >= (1u << l)) // no code may be all 1-bits, as libjpeg requires
       return fail(MDCT_INVALID_PARAMETER, "%s: codes over-subscribed at length %u", name, l);
     code <<= 1;
   }
+  annex_c_codes(sp->bits16, sp->vals, sp->nvals, cap, tab);
   bool all = true;
   if (is_ac)
   {
@@ -409,51 +267,6 @@ int spec_codes(const mdct_jpegenc_opt_spec *sp, bool is_ac, const char *name, ui
     for (int s = 0; s < 12; s++)
       all = all && tab[s];
   *complete = *complete && all;
-  return MDCT_SUCCESS;
-}
-
-int fill_lut(const float *lut, mdct::OwnTables &tb, const char *name)
-{
-  const int bad = mdct::own_tables_fill(lut, tb, /*pair_order=*/true);
-  if (bad >= 0)
-    return fail(MDCT_INVALID_PARAMETER, "%s table entry %d is %g; finite non-zero entries", name, bad, (double)lut[bad]);
-  return MDCT_SUCCESS;
-}
-
-// the three planes of an interleaved scan (the checks of mdct_jpegenc_scan_rows): *h, *v the luma sampling
-int check_mcu_planes(const mdct_jpegenc_scan_plane *planes, int *h, int *v, size_t *mcus_x, size_t *mcus_y)
-{
-  for (int c = 0; c < 3; c++)
-    if (!planes[c].px)
-      return fail(MDCT_INVALID_PARAMETER, "plane %d: null pointer", c);
-  *h = planes[0].h;
-  *v = planes[0].v;
-  if (planes[1].h != 1 || planes[1].v != 1 || planes[2].h != 1 || planes[2].v != 1)
-    return fail(MDCT_INVALID_PARAMETER, "chroma sampling factors %dx%d / %dx%d (1x1)", planes[1].h, planes[1].v, planes[2].h, planes[2].v);
-  if (!((*h == 1 && *v == 1) || (*h == 2 && *v == 1) || (*h == 2 && *v == 2)))
-    return fail(MDCT_INVALID_PARAMETER, "luma sampling factors %dx%d (1x1, 2x1 or 2x2)", *h, *v);
-  *mcus_x = planes[1].width / 8;
-  *mcus_y = planes[1].height / 8;
-  for (int c = 0; c < 3; c++)
-  {
-    const mdct_jpegenc_scan_plane &p = planes[c];
-    if (p.width == 0 || p.height == 0 || p.width > 65536 || p.height > 65536 || p.width != *mcus_x * 8 * (size_t)p.h || p.height != *mcus_y * 8 * (size_t)p.v)
-      return fail(MDCT_INVALID_PARAMETER, "plane %d: %zux%zu at sampling %dx%d is not on the MCU grid of %zux%zu MCUs the chroma planes state (width = mcus_x * 8 * h, "
-                  "height = mcus_y * 8 * v, 8..65536)", c, p.width, p.height, p.h, p.v, *mcus_x, *mcus_y);
-    if (p.pitch < p.width)
-      return fail(MDCT_INVALID_PARAMETER, "plane %d: pitch %zu < width %zu", c, p.pitch, p.width);
-  }
-  return MDCT_SUCCESS;
-}
-
-int check_block_plane(const uint8_t *px, size_t pitch, size_t width, size_t height, int c)
-{
-  if (!px)
-    return fail(MDCT_INVALID_PARAMETER, "plane %d: null pointer", c);
-  if (width == 0 || height == 0 || width % 8 || height % 8 || width > 65536 || height > 65536)
-    return fail(MDCT_INVALID_PARAMETER, "plane %d: %zux%zu (multiples of 8, 8..65536)", c, width, height);
-  if (pitch < width)
-    return fail(MDCT_INVALID_PARAMETER, "plane %d: pitch %zu < width %zu", c, pitch, width);
   return MDCT_SUCCESS;
 }
 
@@ -653,10 +466,8 @@ int mdct_jpegenc_opt_rows(const uint8_t *px, size_t pitch, const float *lut, siz
     return rc;
   if (by0 >= by1 || by1 > sizeY / 8)
     return fail(MDCT_INVALID_PARAMETER, "block rows [%zu, %zu) of %zu", by0, by1, sizeY / 8);
-  const size_t need = mdct_jpegenc_opt_seg_stride(sizeX / 8);
-  if (seg_stride < need || seg_stride % 4 != 0 || ((uintptr_t)out & 3))
-    return fail(MDCT_INVALID_PARAMETER, "seg_stride %zu: a multiple of 4 and >= 209 * %zu blocks per row + 8 = %zu (1665 bits per block); out 4-byte aligned",
-                seg_stride, sizeX / 8, need);
+  if ((rc = check_seg_stride(seg_stride, out, mdct_jpegenc_opt_seg_stride(sizeX / 8), 209, sizeX / 8, "row", "1665 bits per block")))
+    return rc;
   if ((uintptr_t)uncoded & 3)
     return fail(MDCT_INVALID_PARAMETER, "uncoded is not 4-byte aligned");
   OptArgs a;
@@ -695,10 +506,9 @@ int mdct_jpegenc_opt_scan_rows(const mdct_jpegenc_scan_plane *planes, int n_plan
     return rc;
   if (my0 >= my1 || my1 > mcus_y)
     return fail(MDCT_INVALID_PARAMETER, "MCU rows [%zu, %zu) of %zu", my0, my1, mcus_y);
-  const size_t blocks = mcus_x * (size_t)(h * v + 2), need = mdct_jpegenc_opt_seg_stride(blocks);
-  if (seg_stride < need || seg_stride % 4 != 0 || ((uintptr_t)out & 3))
-    return fail(MDCT_INVALID_PARAMETER, "seg_stride %zu: a multiple of 4 and >= 209 * %zu blocks per MCU row + 8 = %zu (1665 bits per block); out 4-byte aligned",
-                seg_stride, blocks, need);
+  const size_t blocks = mcus_x * (size_t)(h * v + 2);
+  if ((rc = check_seg_stride(seg_stride, out, mdct_jpegenc_opt_seg_stride(blocks), 209, blocks, "MCU row", "1665 bits per block")))
+    return rc;
   if ((uintptr_t)uncoded & 3)
     return fail(MDCT_INVALID_PARAMETER, "uncoded is not 4-byte aligned");
   OptArgs a;

@@ -16,26 +16,11 @@
 // tests/jpeg_scaled_checker.py restates these operations in numpy float32, in this order.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "host_error.h"
 #include "launch_tally.h"
 #include "mdct_jpegscale.h"
-
-namespace
-{
-char g_err[512];
-
-int fail(int code, const char *fmt, ...)
-{
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-} // namespace
 
 namespace mdct
 {

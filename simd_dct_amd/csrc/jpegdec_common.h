@@ -4,10 +4,9 @@
 // Each library includes it from exactly one translation unit; everything here has internal linkage or is a device function.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "host_error.h"
 #include "mdct.h"
 #include "mdct_jpegdec.h"
 #include "wg_sync.h"
@@ -15,17 +14,6 @@
 // the message of this library's last failure (each library has its own)
 namespace
 {
-char g_err[512];
-
-int fail(int code, const char *fmt, ...)
-{
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
 int hip_fail(hipError_t e, const char *what) { return fail(MDCT_NOT_SUPPORTED, "%s: %s", what, hipGetErrorString(e)); }
 } // namespace
 

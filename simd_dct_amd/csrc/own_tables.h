@@ -1,5 +1,6 @@
 // own_tables.h -- the multiplier tables of the engine-own paths (OwnTables, mdct_kernels.h), derived on the host.  Shared by
-// mdct_api.hip (libmdct_hip.so) and jpeg_encode_scan.hip (libmdct_jpegenc_scan.so): one derivation, so the same coefficients.
+// mdct_api.hip (libmdct_hip.so) and the scan coders (scan_host.h: libmdct_jpegenc_scan.so, libmdct_jpegenc_opt.so): one derivation, so
+// the same coefficients.
 #pragma once
 #include <cmath>
 #include <cstring>

@@ -139,16 +139,21 @@ def scan_seg_stride(mcus_x, sampling):
     return int(_jpegenc_scan_lib.load().mdct_jpegenc_scan_seg_stride(mcus_x, sum(h * v for h, v in sampling)))
 
 
-def scan_rows(planes, sampling, luts, out, seg_bytes, ff_counts, seg_stride=None, my0=0, my1=None, stream=None, check=True):
-    """mdct_jpegenc_scan_rows on device tensors.  planes: Y, Cb, Cr, uint8 [rows, columns] with contiguous columns, each exactly its size
-    on the MCU grid (mcu_grid); sampling: [(h, v)] per component; luts: (luma, chroma), 64 numbers each in natural order.  out: uint8,
-    one segment per MCU row seg_stride apart (default: scan_seg_stride); seg_bytes / ff_counts: int32 per MCU row.  MCU rows my0 .. my1
-    (default: all) are coded.  Returns the status (raises unless check=False)."""
+def _plane_array(planes, sampling):
     arr = (_jpegenc_scan_lib.Plane * max(1, len(planes)))()
     for k, (p, (h, v)) in enumerate(zip(planes, sampling)):
         if p.dim() != 2 or p.stride(1) != 1 or p.element_size() != 1:
             raise ValueError(f"plane {k}: uint8 tensor [rows, columns] with contiguous columns")
         arr[k] = _jpegenc_scan_lib.Plane(p.data_ptr(), p.stride(0), p.shape[1], p.shape[0], h, v)
+    return arr
+
+
+def scan_rows(planes, sampling, luts, out, seg_bytes, ff_counts, seg_stride=None, my0=0, my1=None, stream=None, check=True):
+    """mdct_jpegenc_scan_rows on device tensors.  planes: Y, Cb, Cr, uint8 [rows, columns] with contiguous columns, each exactly its size
+    on the MCU grid (mcu_grid); sampling: [(h, v)] per component; luts: (luma, chroma), 64 numbers each in natural order.  out: uint8,
+    one segment per MCU row seg_stride apart (default: scan_seg_stride); seg_bytes / ff_counts: int32 per MCU row.  MCU rows my0 .. my1
+    (default: all) are coded.  Returns the status (raises unless check=False)."""
+    arr = _plane_array(planes, sampling)
     tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
     mcus_x, mcus_y = planes[-1].shape[1] // 8, planes[-1].shape[0] // 8
     if seg_stride is None:
@@ -164,15 +169,6 @@ def scan_rows(planes, sampling, luts, out, seg_bytes, ff_counts, seg_stride=None
 def _opt_error(rc):
     lib = _jpegenc_opt_lib.load()
     return api.MdctError(f"mdct_jpegenc_opt status {rc}: {lib.mdct_jpegenc_opt_last_error().decode()}")
-
-
-def _plane_array(planes, sampling):
-    arr = (_jpegenc_scan_lib.Plane * max(1, len(planes)))()
-    for k, (p, (h, v)) in enumerate(zip(planes, sampling)):
-        if p.dim() != 2 or p.stride(1) != 1 or p.element_size() != 1:
-            raise ValueError(f"plane {k}: uint8 tensor [rows, columns] with contiguous columns")
-        arr[k] = _jpegenc_scan_lib.Plane(p.data_ptr(), p.stride(0), p.shape[1], p.shape[0], h, v)
-    return arr
 
 
 def symbol_histogram(planes, sampling, luts, interleaved=False, hist=None, stream=None, check=True):

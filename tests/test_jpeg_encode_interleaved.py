@@ -5,11 +5,14 @@ The expected bytes everywhere: the checker's planes (tests/jpeg_encode_checker.p
 each plane (tests/oracle.py u8_i16, level shift on) and tests/jpeg_scan_encoder.py coding them as one scan of three components with a
 restart interval of one MCU row.
 
-CPU: the container (our reader, the decode checker, Pillow), the C-ABI's refusals, encode_jpeg's argument checks, the code object.
+CPU: the container (our reader, the decode checker, Pillow), the C-ABI's refusals, encode_jpeg's argument checks, the code object, the
+scan-order arithmetic of the kernels (scan_order.h) under sanitizers.
 GPU: scan_rows segment by segment in every instantiation; encode_jpeg's files; agreement with the three-scan path through decode_jpeg;
 full frames; Pillow; a captured graph; the retry when the first buffer is too small."""
 import io
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -188,6 +191,22 @@ def test_code_object_holds_the_planned_instantiations():
     from test_kernel_coverage import code_object_kernels
     names, n_objects = code_object_kernels(lib=SCAN_LIB)
     assert n_objects == 1 and names == set(KERNEL.values()), sorted(names ^ set(KERNEL.values()))
+
+
+def test_scan_order_under_sanitizers(tmp_path):
+    """scan_order.h's seq_block<H, V> -- which LDS row a thread of k_scan_rows / k_opt codes and where its DC predictor lives -- for every
+    thread of the four layouts against T.81 A.2.3 as tests/scan_order_driver.cpp states it: a stand-alone program, sanitizers linked in"""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "scan_order"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "simd_dct_amd", "csrc"), os.path.join(ROOT, "tests", "scan_order_driver.cpp"),
+                        "-o", str(exe)], capture_output=True, text=True)
+    if r.returncode != 0 and "san" in (r.stderr + r.stdout).lower() and "cannot find" in (r.stderr + r.stdout).lower():
+        pytest.skip("sanitizer runtime not installed: " + r.stderr[-200:])
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "scan order ok" in r.stdout, r.stdout + r.stderr
 
 
 # ------------------------------------------------------------------------------------------ GPU
