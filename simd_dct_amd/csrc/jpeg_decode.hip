@@ -22,9 +22,7 @@
 // Byte unstuffing happens in the bit reader; positions a lane hands to the next are counted in bits after unstuffing from the next
 // sub-sequence's first data byte, so both lanes count the same way.  Every loop has a bound; no workgroup waits for another.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "jpegdec_common.h"
@@ -44,18 +42,11 @@ __global__ void __launch_bounds__(kThreads) k_decode(DecArgs a)
   __shared__ uint32_t first_err, fin_word, fail_unit;
   const int tid = threadIdx.x;
   const uint32_t k = blockIdx.x;
+  load_tables(a, T, lcomp, tid);
+  if (tid == 0)
   {
-    const uint32_t *src = (const uint32_t *)a.tab;
-    uint32_t *dst = (uint32_t *)&T;
-    for (int i = tid; i < (int)(sizeof(DevTables) / 4); i += kThreads)
-      dst[i] = src[i];
-    if (tid < 16)
-      lcomp[tid] = tid < (int)a.upm ? a.bcomp[tid] : 0;
-    if (tid == 0)
-    {
-      first_err = kNone;
-      fin_word = kNone;
-    }
+    first_err = kNone;
+    fin_word = kNone;
   }
   // the interval's data, clamped into the scan whatever the offsets say
   const uint64_t len = a.scan_len;
@@ -71,102 +62,47 @@ __global__ void __launch_bounds__(kThreads) k_decode(DecArgs a)
   if (!last && next <= len)
     for (uint64_t i = 0, n = e - s; i < n && a.scan[e - 1] == 0xFF; i++)
       e--;
-  const uint64_t nbytes = e - s;
-  uint64_t sb = (nbytes + kThreads - 1) / kThreads;
-  sb = sb < 8 ? 8 : sb;
-  const uint32_t nact = nbytes ? (uint32_t)((nbytes + sb - 1) / sb) : 1u;
+  const uint64_t sb = (e - s + kThreads - 1) / kThreads;
+  const SubLane q = sub_lane(s, e, sb < 8 ? 8 : sb, tid, true);
   const uint32_t mcu0 = k * a.restart;
   const uint32_t nmcu = (a.total_mcus - mcu0) < a.restart ? a.total_mcus - mcu0 : a.restart;
-  const uint32_t units = nmcu * a.upm;
-  const bool active = (uint32_t)tid < nact;
-  const uint64_t s0 = s + (uint64_t)tid * sb;
-  const uint64_t E = (uint32_t)tid + 1 < nact ? s0 + sb : ~uint64_t(0);
-  const uint64_t cap = 8 * (e - (s0 < e ? s0 : e)) + 64;
+  const uint32_t units = nmcu * a.g.upm;
   wg_sync();
 
   // ---- synchronisation: lane 0 starts exact, the others from a guess, until no start changes
   Lane L;
-  Reader r;
   uint32_t my_start = 0;
-  int dummy[3] = {0, 0, 0};
-  if (active)
-  {
-    reader_init(r, a, s0, e, E, tid == 0);
-    run<false>(r, a, T, lcomp, my_start, L, 0, 0, 0, dummy, cap);
-  }
-  else
-  {
-    L.state = kErr;
-    L.blocks = 0;
-    L.dc[0] = L.dc[1] = L.dc[2] = 0;
-  }
-  exit_state[tid] = L.state;
-  for (uint32_t round = 0; round <= nact; round++)
-  {
-    wg_sync();
-    const uint32_t want = tid == 0 ? 0u : exit_state[tid - 1];
-    const bool changed = active && want != my_start;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!__syncthreads_or(changed))
-      break;
-    if (changed)
-    {
-      my_start = want;
-      reader_init(r, a, s0, e, E, tid == 0);
-      run<false>(r, a, T, lcomp, my_start, L, 0, 0, 0, dummy, cap);
-      exit_state[tid] = L.state;
-    }
-  }
+  speculate(a, T, lcomp, q, my_start, L);
+  settle(a, T, lcomp, q, 0u, my_start, L, exit_state);
 
-  // ---- blocks before each lane's start, and the DC predictors there
-  const int unit0 = wg_excl_scan(active ? L.blocks : 0, wtot);
+  // ---- blocks before each lane's start, and the DC predictors there (an idle lane counts nothing)
+  const uint32_t unit0 = (uint32_t)wg_excl_scan(L.blocks, wtot);
   int pred[3];
   for (int c = 0; c < 3; c++)
-    pred[c] = wg_excl_scan(active ? L.dc[c] : 0, wtot);
+    pred[c] = wg_excl_scan(L.dc[c], wtot);
 
-  // ---- zero the interval's blocks (consecutive lanes: consecutive blocks of one MCU row, same pixel row)
-  for (uint32_t wi = tid; wi < units * 8; wi += kThreads)
-  {
-    const uint32_t unit = wi % units, row = wi / units;
-    const uint32_t mcu = mcu0 + unit / a.upm, b = unit % a.upm, c = a.bcomp[b];
-    const uint32_t my = mcu / a.mcus_x, mx = mcu - my * a.mcus_x;
-    int16_t *p = a.plane[c] + ((size_t)(my * a.cv[c] + a.bv[b]) * 8 + row) * a.pitch[c] + (size_t)(mx * a.ch[c] + a.bh[b]) * 8;
-    *(uint4 *)p = make_uint4(0, 0, 0, 0);
-  }
+  // ---- zero the interval's blocks.  The stores are numbered in 32 bits, whose division costs a fraction of the 64-bit one: units * 8 +
+  // kThreads stays below 2^32 for an interval of fewer than 2^29 - 32 blocks (64 GiB of coefficients), and this kernel has never
+  // zeroed a longer one
+  zero_units<uint32_t>(a.g, mcu0, 0, units, tid, kThreads);
   __threadfence_block();
   wg_sync();
 
   // ---- the decode proper
-  Lane F;
-  F.blocks = 0;
-  if (active)
-  {
-    reader_init(r, a, s0, e, E, tid == 0);
-    run<true>(r, a, T, lcomp, my_start, F, (uint32_t)unit0, units, mcu0, pred, cap);
-    if (F.err && (uint32_t)unit0 < units)
-      atomicMin(&first_err, ((uint32_t)tid << 8) | F.err);
-    if (F.finished)
-      fin_word = F.fin;
-  }
+  uint32_t stop = 0;
+  if (q.active)
+    stop = write_pass(a, T, lcomp, q, my_start, unit0, units, mcu0, pred, &first_err, &fin_word);
   wg_sync();
   if (first_err != kNone)
   {
     // The lanes after the one that met the interval's first error started from states of the speculating passes, which carry on past
     // such an error: what they wrote lies in blocks after the failing one and means nothing.  Those blocks go back to zero; the
-    // failing block keeps the levels decoded before the error (unit0 + F.blocks < units in the lane that reported it).
+    // failing block keeps the levels decoded before the error (stop < units in the lane that reported it).
     if ((uint32_t)tid == first_err >> 8)
-      fail_unit = (uint32_t)unit0 + (uint32_t)F.blocks;
+      fail_unit = stop;
     __threadfence();
     wg_sync();
-    const uint32_t z0 = fail_unit + 1, nz = units - z0;
-    for (uint32_t wi = tid; wi < nz * 8; wi += kThreads)
-    {
-      const uint32_t unit = z0 + wi % nz, row = wi / nz;
-      const uint32_t mcu = mcu0 + unit / a.upm, b = unit % a.upm, c = a.bcomp[b];
-      const uint32_t my = mcu / a.mcus_x, mx = mcu - my * a.mcus_x;
-      int16_t *p = a.plane[c] + ((size_t)(my * a.cv[c] + a.bv[b]) * 8 + row) * a.pitch[c] + (size_t)(mx * a.ch[c] + a.bh[b]) * 8;
-      *(uint4 *)p = make_uint4(0, 0, 0, 0);
-    }
+    zero_units<uint32_t>(a.g, mcu0, fail_unit + 1, units - (fail_unit + 1), tid, kThreads);
   }
   if (tid == 0)
   {
@@ -235,29 +171,7 @@ __global__ void __launch_bounds__(kThreads) k_rst_walk(IndexArgs a)
 __global__ void __launch_bounds__(1024) k_rst_scan(IndexArgs a)
 {
   __shared__ int wtot[16];
-  const uint32_t per = (a.nchunks + 1023) / 1024;
-  const uint32_t c0 = threadIdx.x * per, c1 = c0 + per < a.nchunks ? c0 + per : a.nchunks;
-  uint32_t n = 0;
-  for (uint32_t c = c0; c < c1; c++)
-    n += a.counts[c];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int inc = wave_incl_scan((int)n, lane);
-  if (lane == 63)
-    wtot[w] = inc;
-  wg_sync();
-  int wb = 0, total = 0;
-  for (int j = 0; j < 16; j++)
-  {
-    wb += j < w ? wtot[j] : 0;
-    total += wtot[j];
-  }
-  uint32_t run_ = (uint32_t)(wb + inc) - n;
-  for (uint32_t c = c0; c < c1; c++)
-  {
-    const uint32_t m = a.counts[c];
-    a.counts[c] = run_;
-    run_ += m;
-  }
+  const uint32_t total = wg1024_excl_prefix(a.counts, a.counts, a.nchunks, wtot);
   if (threadIdx.x == 0)
   {
     a.off[0] = 0;
@@ -271,62 +185,6 @@ __global__ void __launch_bounds__(1024) k_rst_scan(IndexArgs a)
 } // namespace mdct
 
 using namespace mdct::jpegdec;
-
-
-static int build_tables(const uint8_t *const bits16[4], const uint8_t *const vals[4], const int nvals[4], DevTables *out, bool present[4])
-{
-  if (!bits16 || !vals || !nvals)
-    return fail(MDCT_INVALID_PARAMETER, "null table arrays");
-  if (out)
-    memset(out, 0, sizeof(*out));
-  for (int t = 0; t < 4; t++)
-  {
-    present[t] = bits16[t] != nullptr;
-    if (!present[t])
-      continue;
-    if (!vals[t] && nvals[t] > 0)
-      return fail(MDCT_INVALID_PARAMETER, "slot %d: null values", t);
-    if (nvals[t] < 0 || nvals[t] > 256)
-      return fail(MDCT_INVALID_PARAMETER, "slot %d: %d values (at most 256)", t, nvals[t]);
-    int total = 0;
-    for (int l = 0; l < 16; l++)
-      total += bits16[t][l];
-    if (total != nvals[t])
-      return fail(MDCT_INVALID_PARAMETER, "slot %d: the 16 counts add up to %d codes, %d values given", t, total, nvals[t]);
-    for (int i = 0; i < total; i++)
-    {
-      const int v = vals[t][i];
-      if (t < 2 ? v > 11 : (v & 15) > 10)
-        return fail(MDCT_INVALID_PARAMETER, "slot %d: value 0x%02x is not a baseline %s symbol", t, v, t < 2 ? "DC" : "AC");
-    }
-    // canonical codes (C.2); no code may be all 1-bits, as libjpeg requires
-    int code = 0, p = 0;
-    for (int l = 1; l <= 16; l++)
-    {
-      const int n = bits16[t][l - 1];
-      if (out)
-      {
-        out->limit[t][l] = n ? (code + n) << (16 - l) : 0;
-        out->delta[t][l] = p - code;
-        if (l <= kFastBits)
-          for (int i = 0; i < n; i++)
-            for (int f = (code + i) << (kFastBits - l); f < (code + i + 1) << (kFastBits - l); f++)
-              out->fast[t][f] = (uint16_t)((l << 8) | vals[t][p + i]);
-      }
-      code += n;
-      p += n;
-      if (code >= (1 << l))
-        return fail(MDCT_INVALID_PARAMETER, "slot %d: codes over-subscribed at length %d", t, l);
-      code <<= 1;
-    }
-    if (out)
-    {
-      out->limit[t][17] = 0x7FFFFFFF;
-      memcpy(out->vals[t], vals[t], (size_t)total);
-    }
-  }
-  return MDCT_SUCCESS;
-}
 
 extern "C" {
 
@@ -379,14 +237,8 @@ int mdct_jpegdec_tables_destroy(mdct_jpegdec_tables *tables)
 
 static int check_desc(const mdct_jpegdec_scan *d, size_t *n_intervals)
 {
-  if (!d)
-    return fail(MDCT_INVALID_PARAMETER, "null scan descriptor");
-  if (d->n_components < 1 || d->n_components > MDCT_JPEGDEC_MAX_COMPONENTS)
-    return fail(MDCT_INVALID_PARAMETER, "%d components (1..3)", d->n_components);
-  if (d->mcus_x == 0 || d->mcus_y == 0 || d->restart_interval == 0)
-    return fail(MDCT_INVALID_PARAMETER, "empty MCU grid or restart interval 0 (scans without restart markers are not supported)");
-  const int rc = check_components(d);
-  if (rc)
+  int rc = check_scan_head(d, true, "empty MCU grid or restart interval 0 (scans without restart markers are not supported)");
+  if (rc || (rc = check_components(d)))
     return rc;
   *n_intervals = (d->mcus_x * d->mcus_y + d->restart_interval - 1) / d->restart_interval;
   return MDCT_SUCCESS;

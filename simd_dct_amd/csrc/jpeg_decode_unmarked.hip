@@ -3,8 +3,8 @@
 //
 // Built into its own library, libmdct_jpegdec_unmarked.so, linked against libmdct_jpegdec.so (whose table handle it accepts) and
 // libmdct_hip.so (whose launch tally counts its launches).  A scan without markers is one interval of up to several MB; k_decode's
-// sub-sequence synchronisation (jpeg_decode.hip) is lifted one level: the stuffed scan is cut into chunks of kThreads sub-sequences of
-// kSubBytes bytes, one workgroup per chunk, and the chunks are synchronised with each other across kernel boundaries only.
+// sub-sequence synchronisation (jpegdec_common.h: speculate, settle) is lifted one level: the stuffed scan is cut into chunks of kThreads
+// sub-sequences of kSubBytes bytes, one workgroup per chunk, and the chunks are synchronised with each other across kernel boundaries only.
 //
 //   k_um_zero    every block the descriptor names, zeroed with 16-byte stores
 //   k_um_sync    one workgroup per chunk: lane 0 of chunk 0 starts exact, lane 0 of every other chunk from a guess (bit 0 of its first
@@ -70,68 +70,6 @@ struct UmArgs
   uint32_t *cerr, *ccnt; // [nchunks]: first error in the chunk (lane << 8 | code, kNone), blocks before it
 };
 
-struct ChunkLane
-{
-  uint64_t s0, E, cap;
-  uint32_t nact;
-  bool active;
-  uint64_t g; // global lane index
-};
-
-__device__ __forceinline__ ChunkLane chunk_lane(const UmArgs &a, uint32_t c, int tid)
-{
-  ChunkLane q;
-  const uint64_t L = a.d.scan_len, c0 = (uint64_t)c * kChunkBytes;
-  const uint64_t cb = L > c0 ? (L - c0 < kChunkBytes ? L - c0 : kChunkBytes) : 0;
-  q.nact = cb ? (uint32_t)((cb + kSubBytes - 1) / kSubBytes) : 1u;
-  q.active = (uint32_t)tid < q.nact;
-  q.s0 = c0 + (uint64_t)tid * kSubBytes;
-  q.E = q.s0 + kSubBytes < L ? q.s0 + kSubBytes : ~uint64_t(0);
-  q.cap = 8 * (L - (q.s0 < L ? q.s0 : L)) + 64;
-  q.g = (uint64_t)c * kThreads + tid;
-  return q;
-}
-
-__device__ __forceinline__ void load_tables(const UmArgs &a, DevTables &T, uint32_t *lcomp, int tid)
-{
-  const uint32_t *src = (const uint32_t *)a.d.tab;
-  uint32_t *dst = (uint32_t *)&T;
-  for (int i = tid; i < (int)(sizeof(DevTables) / 4); i += kThreads)
-    dst[i] = src[i];
-  if (tid < 16)
-    lcomp[tid] = tid < (int)a.d.upm ? a.d.bcomp[tid] : 0;
-}
-
-// The intra-chunk loop of k_decode: lane 0 wants want0, lane i the exit of lane i - 1; a lane whose start differs decodes again, until no
-// start changes (at most nact + 1 trips: each trip makes one more lane exact).  Returns whether this lane decoded again.
-__device__ bool settle(const UmArgs &a, const DevTables &T, const uint32_t *lcomp, const ChunkLane &q, uint32_t want0, uint32_t &my_start,
-                       Lane &L, uint32_t *exit_state)
-{
-  Reader r;
-  int dummy[3] = {0, 0, 0};
-  bool ran = false;
-  exit_state[threadIdx.x] = L.state;
-  for (uint32_t round = 0; round <= q.nact; round++)
-  {
-    wg_sync();
-    const uint32_t want = threadIdx.x == 0 ? want0 : exit_state[threadIdx.x - 1];
-    const bool changed = q.active && want != my_start;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!__syncthreads_or(changed))
-      break;
-    if (changed)
-    {
-      my_start = want;
-      reader_init(r, a.d, q.s0, a.d.scan_len, q.E, q.g == 0);
-      run<false>(r, a.d, T, lcomp, my_start, L, 0, 0, 0, dummy, q.cap);
-      exit_state[threadIdx.x] = L.state;
-      ran = true;
-    }
-  }
-  wg_sync();
-  return ran;
-}
-
 // the chunk's totals (blocks, DC sums) into ctot
 __device__ void chunk_totals(const UmArgs &a, uint32_t c, const Lane &L, bool active, int *tot)
 {
@@ -160,15 +98,7 @@ __device__ __forceinline__ void store_lane(const UmArgs &a, uint64_t g, uint32_t
 
 __global__ void __launch_bounds__(kThreads) k_um_zero(UmArgs a)
 {
-  const uint64_t n = (uint64_t)a.units * 8;
-  for (uint64_t wi = (uint64_t)blockIdx.x * kThreads + threadIdx.x; wi < n; wi += (uint64_t)gridDim.x * kThreads)
-  {
-    const uint32_t row = (uint32_t)(wi / a.units), unit = (uint32_t)(wi - (uint64_t)row * a.units);
-    const uint32_t mcu = unit / a.d.upm, b = unit - mcu * a.d.upm, c = a.d.bcomp[b];
-    const uint32_t my = mcu / a.d.mcus_x, mx = mcu - my * a.d.mcus_x;
-    int16_t *p = a.d.plane[c] + ((size_t)(my * a.d.cv[c] + a.d.bv[b]) * 8 + row) * a.d.pitch[c] + (size_t)(mx * a.d.ch[c] + a.d.bh[b]) * 8;
-    *(uint4 *)p = make_uint4(0, 0, 0, 0);
-  }
+  zero_units<uint64_t>(a.d.g, 0, 0, a.units, (uint64_t)blockIdx.x * kThreads + threadIdx.x, (uint64_t)gridDim.x * kThreads);
 }
 
 __global__ void __launch_bounds__(kThreads) k_um_sync(UmArgs a)
@@ -179,28 +109,16 @@ __global__ void __launch_bounds__(kThreads) k_um_sync(UmArgs a)
   __shared__ int tot[4];
   const int tid = threadIdx.x;
   const uint32_t c = blockIdx.x;
-  load_tables(a, T, lcomp, tid);
+  load_tables(a.d, T, lcomp, tid);
   if (c == 0 && tid == 0)
     a.ctl[kLastRound] = 0;
-  const ChunkLane q = chunk_lane(a, c, tid);
+  const SubLane q = sub_lane((uint64_t)c * kChunkBytes, a.d.scan_len, kSubBytes, tid, c == 0); // lane 0 of chunk 0 starts exact
   wg_sync();
   Lane L;
   uint32_t my_start = 0;
-  if (q.active)
-  {
-    Reader r;
-    int dummy[3] = {0, 0, 0};
-    reader_init(r, a.d, q.s0, a.d.scan_len, q.E, q.g == 0);
-    run<false>(r, a.d, T, lcomp, my_start, L, 0, 0, 0, dummy, q.cap);
-  }
-  else
-  {
-    L.state = kErr;
-    L.blocks = 0;
-    L.dc[0] = L.dc[1] = L.dc[2] = 0;
-  }
-  settle(a, T, lcomp, q, 0u, my_start, L, exit_state); // lane 0 keeps its start: exact in chunk 0, the guess elsewhere
-  store_lane(a, q.g, my_start, L, q.active);
+  speculate(a.d, T, lcomp, q, my_start, L);
+  settle(a.d, T, lcomp, q, 0u, my_start, L, exit_state); // lane 0 keeps its start: exact in chunk 0, the guess elsewhere
+  store_lane(a, (uint64_t)c * kThreads + tid, my_start, L, q.active);
   chunk_totals(a, c, L, q.active, tot);
   if (tid == 0)
     a.pub[c] = exit_state[q.nact - 1];
@@ -215,8 +133,8 @@ __global__ void __launch_bounds__(kThreads) k_um_round(UmArgs a, uint32_t rnd)
   __shared__ uint32_t go, want0;
   const int tid = threadIdx.x;
   const uint32_t c = blockIdx.x;
-  const ChunkLane q = chunk_lane(a, c, tid);
-  const uint64_t g_last = (uint64_t)c * kThreads + q.nact - 1;
+  const SubLane q = sub_lane((uint64_t)c * kChunkBytes, a.d.scan_len, kSubBytes, tid, c == 0); // lane 0 of chunk 0 starts exact
+  const uint64_t g = (uint64_t)c * kThreads + tid, g_last = (uint64_t)c * kThreads + q.nact - 1; // indices among all lanes
   uint32_t *pub_now = a.pub + (size_t)(rnd & 1) * a.nchunks;
   if (tid == 0)
   {
@@ -232,19 +150,17 @@ __global__ void __launch_bounds__(kThreads) k_um_round(UmArgs a, uint32_t rnd)
   wg_sync();
   if (!go)
     return;
-  load_tables(a, T, lcomp, tid);
-  uint32_t my_start = a.start[q.g];
+  load_tables(a.d, T, lcomp, tid);
+  uint32_t my_start = a.start[g];
   Lane L;
-  L.state = a.exit_[q.g];
-  L.blocks = a.blocks[q.g];
+  L.state = a.exit_[g]; // a lane without data: kErr, no blocks, no DC, as k_um_sync stored them for all nlanes of this scan (store_lane)
+  L.blocks = a.blocks[g];
   for (int k = 0; k < 3; k++)
-    L.dc[k] = a.dc[(size_t)k * a.nlanes + q.g];
+    L.dc[k] = a.dc[(size_t)k * a.nlanes + g];
   const uint32_t old_exit = a.exit_[g_last];
-  if (!q.active)
-    L.state = kErr;
   wg_sync();
-  if (settle(a, T, lcomp, q, want0, my_start, L, exit_state))
-    store_lane(a, q.g, my_start, L, q.active);
+  if (settle(a.d, T, lcomp, q, want0, my_start, L, exit_state))
+    store_lane(a, g, my_start, L, q.active);
   chunk_totals(a, c, L, q.active, tot);
   if (tid == 0)
   {
@@ -253,38 +169,6 @@ __global__ void __launch_bounds__(kThreads) k_um_round(UmArgs a, uint32_t rnd)
     if (e != old_exit)
       atomicMax(&a.ctl[kLastRound], rnd);
   }
-}
-
-// exclusive prefix over the chunks of ctot[k] into cbase[k] (one workgroup of 1024); returns the total
-__device__ int chunk_prefix(const UmArgs &a, int k, int *wtot)
-{
-  const uint32_t per = (a.nchunks + 1023) / 1024;
-  const uint32_t c0 = threadIdx.x * per, c1 = c0 + per < a.nchunks ? c0 + per : a.nchunks;
-  const int *src = a.ctot + (size_t)k * a.nchunks;
-  int *dst = a.cbase + (size_t)k * a.nchunks;
-  int n = 0;
-  for (uint32_t c = c0; c < c1; c++)
-    n += src[c];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int inc = wave_incl_scan(n, lane);
-  if (lane == 63)
-    wtot[w] = inc;
-  wg_sync();
-  int wb = 0, total = 0;
-  for (int j = 0; j < 16; j++)
-  {
-    wb += j < w ? wtot[j] : 0;
-    total += wtot[j];
-  }
-  int run_ = wb + inc - n;
-  for (uint32_t c = c0; c < c1; c++)
-  {
-    const int m = src[c];
-    dst[c] = run_;
-    run_ += m;
-  }
-  wg_sync();
-  return total;
 }
 
 __global__ void __launch_bounds__(1024) k_um_prefix(UmArgs a)
@@ -305,9 +189,9 @@ __global__ void __launch_bounds__(1024) k_um_prefix(UmArgs a)
         atomicMin(&loose, c);
     }
   const bool ok = !__syncthreads_or(bad);
-  const int total = chunk_prefix(a, 0, wtot);
-  for (int k = 1; k < 4; k++)
-    chunk_prefix(a, k, wtot);
+  const int total = wg1024_excl_prefix(a.ctot, a.cbase, a.nchunks, wtot); // blocks
+  for (int k = 1; k < 4; k++)                                             // DC sums
+    wg1024_excl_prefix(a.ctot + (size_t)k * a.nchunks, a.cbase + (size_t)k * a.nchunks, a.nchunks, wtot);
   if (threadIdx.x == 0)
   {
     a.ctl[kSyncOk] = ok;
@@ -333,32 +217,23 @@ __global__ void __launch_bounds__(kThreads) k_um_write(UmArgs a)
       a.cerr[c] = kNone;
     return;
   }
-  load_tables(a, T, lcomp, tid);
+  load_tables(a.d, T, lcomp, tid);
   if (tid == 0)
     first_err = kNone;
-  const ChunkLane q = chunk_lane(a, c, tid);
-  const int nb = q.active ? a.blocks[q.g] : 0;
-  const int unit0 = a.cbase[c] + wg_excl_scan(nb, wtot);
+  const SubLane q = sub_lane((uint64_t)c * kChunkBytes, a.d.scan_len, kSubBytes, tid, c == 0); // lane 0 of chunk 0 starts exact
+  const uint64_t g = (uint64_t)c * kThreads + tid;
+  const int nb = q.active ? a.blocks[g] : 0;
+  const uint32_t unit0 = (uint32_t)(a.cbase[c] + wg_excl_scan(nb, wtot));
   int pred[3];
   for (int k = 0; k < 3; k++)
-    pred[k] = a.cbase[(size_t)(1 + k) * a.nchunks + c] + wg_excl_scan(q.active ? a.dc[(size_t)k * a.nlanes + q.g] : 0, wtot);
-  Lane F;
-  F.err = 0;
-  F.blocks = 0;
-  if (q.active)
-  {
-    Reader r;
-    reader_init(r, a.d, q.s0, a.d.scan_len, q.E, q.g == 0);
-    run<true>(r, a.d, T, lcomp, a.start[q.g], F, (uint32_t)unit0, a.units, 0, pred, q.cap);
-    if (F.err && (uint32_t)unit0 < a.units)
-      atomicMin(&first_err, ((uint32_t)tid << 8) | F.err);
-    if (F.finished)
-      a.ctl[kFin] = F.fin; // one lane of the whole scan completes its last block
-  }
+    pred[k] = a.cbase[(size_t)(1 + k) * a.nchunks + c] + wg_excl_scan(q.active ? a.dc[(size_t)k * a.nlanes + g] : 0, wtot);
+  uint32_t stop = 0;
+  if (q.active) // (one lane of the whole scan completes its last block and writes kFin)
+    stop = write_pass(a.d, T, lcomp, q, a.start[g], unit0, a.units, 0, pred, &first_err, &a.ctl[kFin]);
   wg_sync();
   const uint32_t fe = first_err;
   if (fe != kNone && (uint32_t)tid == fe >> 8)
-    a.ccnt[c] = (uint32_t)unit0 + (uint32_t)F.blocks;
+    a.ccnt[c] = stop;
   if (tid == 0)
     a.cerr[c] = fe;
 }
@@ -417,15 +292,7 @@ __global__ void __launch_bounds__(1024) k_um_final(UmArgs a)
   // After an error the lanes and chunks behind it wrote levels of the re-synchronised decode into blocks after the failing one (block n):
   // those go back to zero.  Block n keeps the levels decoded before the error.  An error path only: one workgroup is enough.
   const uint32_t z0 = zero_from < a.units ? zero_from : a.units;
-  const uint64_t nz = a.units - z0;
-  for (uint64_t wi = threadIdx.x; wi < nz * 8; wi += 1024)
-  {
-    const uint32_t row = (uint32_t)(wi / nz), unit = z0 + (uint32_t)(wi - (uint64_t)row * nz);
-    const uint32_t mcu = unit / a.d.upm, b = unit - mcu * a.d.upm, c = a.d.bcomp[b];
-    const uint32_t my = mcu / a.d.mcus_x, mx = mcu - my * a.d.mcus_x;
-    int16_t *p = a.d.plane[c] + ((size_t)(my * a.d.cv[c] + a.d.bv[b]) * 8 + row) * a.d.pitch[c] + (size_t)(mx * a.d.ch[c] + a.d.bh[b]) * 8;
-    *(uint4 *)p = make_uint4(0, 0, 0, 0);
-  }
+  zero_units<uint64_t>(a.d.g, 0, z0, a.units - z0, threadIdx.x, 1024);
 }
 
 } // namespace jpegdec
@@ -467,14 +334,9 @@ Layout layout(size_t scan_len)
 
 int check_unmarked(const mdct_jpegdec_scan *d, size_t scan_len)
 {
-  if (!d)
-    return fail(MDCT_INVALID_PARAMETER, "null scan descriptor");
-  if (d->n_components < 1 || d->n_components > MDCT_JPEGDEC_MAX_COMPONENTS)
-    return fail(MDCT_INVALID_PARAMETER, "%d components (1..3)", d->n_components);
-  if (d->mcus_x == 0 || d->mcus_y == 0)
-    return fail(MDCT_INVALID_PARAMETER, "empty MCU grid");
-  if (d->restart_interval != 0)
-    return fail(MDCT_INVALID_PARAMETER, "restart interval %zu: a scan with restart markers goes to mdct_jpegdec_decode", d->restart_interval);
+  const int rc = check_scan_head(d, false, "restart interval %zu: a scan with restart markers goes to mdct_jpegdec_decode");
+  if (rc)
+    return rc;
   if (scan_len >= kMaxScan)
     return fail(MDCT_NOT_SUPPORTED, "scan of %zu bytes (less than 2^28)", scan_len);
   return check_components(d);
@@ -515,7 +377,7 @@ int mdct_jpegdec_decode_unmarked(const mdct_jpegdec_scan *desc, const mdct_jpegd
   a.status = status;
   a.nchunks = (uint32_t)l.nchunks;
   a.nlanes = l.nlanes;
-  a.units = a.d.total_mcus * a.d.upm;
+  a.units = a.d.total_mcus * a.d.g.upm;
   a.rounds = l.nchunks > 1 ? (uint32_t)sync_rounds : 0u;
   a.ctl = (uint32_t *)w;
   a.start = (uint32_t *)(w + l.start);

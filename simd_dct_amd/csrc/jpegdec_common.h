@@ -1,14 +1,14 @@
 // jpegdec_common.h -- what the two JPEG decoder libraries share (jpeg_decode.hip: restart-marked scans, libmdct_jpegdec.so;
 // jpeg_decode_unmarked.hip: scans without restart markers, libmdct_jpegdec_unmarked.so): the device Huffman tables and the handle
-// that owns them, the bit reader with its unstuffing, the Huffman lookup, the sub-sequence decoder `run` and the workgroup prefix sums.
+// that owns them (huff_tables.h), the block layout (block_place.h), the bit reader with its unstuffing, the Huffman lookup, the
+// sub-sequence decoder `run`, the skeleton both decoders hang it in -- a lane's sub-sequence (SubLane), the speculative first pass, the
+// settle loop that synchronises the lanes of a workgroup, the write pass -- the workgroup prefix sums and the host's descriptor checks.
 // Each library includes it from exactly one translation unit; everything here has internal linkage or is a device function.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdint.h>
 
-#include "host_error.h"
-#include "mdct.h"
-#include "mdct_jpegdec.h"
+#include "block_place.h" // mdct_jpegdec.h
+#include "huff_tables.h" // host_error.h, mdct.h
 #include "wg_sync.h"
 
 // the message of this library's last failure (each library has its own)
@@ -23,20 +23,8 @@ namespace jpegdec
 {
 
 constexpr int kThreads = 256;   // lanes per restart interval
-constexpr int kFastBits = 9;    // codes up to 9 bits resolve in one LDS lookup
 constexpr uint32_t kErr = 0x80000000u;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-
-// T.81 C.2 / F.2.2.3, built on the host: fast[peek9] = (length << 8) | value for codes of <= 9 bits (0: longer code or none);
-// a 16-bit left-justified code c has length l if c < limit[l] (first such l), and its value is vals[(c >> (16 - l)) + delta[l]].
-struct DevTables
-{
-  uint16_t fast[4][1 << kFastBits];
-  int32_t limit[4][18];
-  int32_t delta[4][18];
-  uint8_t vals[4][256];
-};
-static_assert(sizeof(DevTables) % 4 == 0, "LDS copy in words");
 
 struct DecArgs
 {
@@ -45,13 +33,9 @@ struct DecArgs
   const uint64_t *off;
   uint32_t *status;
   const DevTables *tab;
-  int16_t *plane[3];
-  uint64_t pitch[3];
-  uint32_t upm;                 // blocks per MCU
-  uint8_t bcomp[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU], bh[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU], bv[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU];
-  uint8_t bdc[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU], bac[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU];
-  uint32_t ch[3], cv[3];        // h, v per component
-  uint32_t mcus_x, total_mcus, restart;
+  BlockPlace g;                 // where block b of MCU m lies
+  uint8_t bdc[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU], bac[MDCT_JPEGDEC_MAX_BLOCKS_PER_MCU]; // table slots of block b
+  uint32_t total_mcus, restart;
   uint32_t n_intervals;
 };
 
@@ -246,15 +230,15 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
   if (WRITE && unit >= units)
     return;
   // the current block's place (WRITE): MCU (mx, my), block b of it
-  uint32_t mcu = 0, mx = 0, my = 0;
+  uint32_t mx = 0, my = 0;
   int16_t *bp = nullptr;
   uint32_t comp = lcomp[b];
   if (WRITE)
   {
-    mcu = mcu0 + unit / a.upm;
-    my = mcu / a.mcus_x;
-    mx = mcu - my * a.mcus_x;
-    bp = a.plane[comp] + (size_t)(my * a.cv[comp] + a.bv[b]) * 8 * a.pitch[comp] + (size_t)(mx * a.ch[comp] + a.bh[b]) * 8;
+    const uint32_t mcu = mcu0 + unit / a.g.upm;
+    my = mcu / a.g.mcus_x;
+    mx = mcu - my * a.g.mcus_x;
+    bp = block_at(a.g, mx, my, b, comp, 0);
   }
   for (uint64_t it = 0; it < cap; it++)
   {
@@ -341,7 +325,7 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
         if (WRITE)
         {
           const uint32_t z = kZigzag[k];
-          bp[(size_t)(z >> 3) * a.pitch[comp] + (z & 7)] = (int16_t)v;
+          bp[(size_t)(z >> 3) * a.g.pitch[comp] + (z & 7)] = (int16_t)v;
         }
         k++;
         block_end = k == 64;
@@ -351,7 +335,7 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
     {
       k = 0;
       out.blocks++;
-      if (++b == a.upm)
+      if (++b == a.g.upm)
         b = 0;
       comp = lcomp[b];
       if (WRITE)
@@ -371,12 +355,12 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
           out.fin = fin;
           return;
         }
-        if (b == 0 && ++mx == a.mcus_x)
+        if (b == 0 && ++mx == a.g.mcus_x)
         {
           mx = 0;
           my++;
         }
-        bp = a.plane[comp] + (size_t)(my * a.cv[comp] + a.bv[b]) * 8 * a.pitch[comp] + (size_t)(mx * a.ch[comp] + a.bh[b]) * 8;
+        bp = block_at(a.g, mx, my, b, comp, 0);
       }
     }
   }
@@ -394,7 +378,7 @@ __device__ __forceinline__ int wave_incl_scan(int x, int lane)
   return x;
 }
 
-// exclusive prefix of x over the workgroup (kThreads lanes)
+// exclusive prefix of x over a workgroup of any number of waves, 4 or 16 here (wtot: an int per wave, each wave adding those before its own)
 __device__ __forceinline__ int wg_excl_scan(int x, int *wtot)
 {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -409,6 +393,125 @@ __device__ __forceinline__ int wg_excl_scan(int x, int *wtot)
   return base + inc - x;
 }
 
+// exclusive prefix of src[0 .. n) into dst (which may be src) over one workgroup of 1024 lanes (wtot: 16 ints); returns the total
+template <class T>
+__device__ T wg1024_excl_prefix(const T *src, T *dst, uint32_t n, int *wtot)
+{
+  const uint32_t per = (n + 1023) / 1024;
+  const uint32_t c0 = threadIdx.x * per, c1 = c0 + per < n ? c0 + per : n;
+  T sum = 0;
+  for (uint32_t c = c0; c < c1; c++)
+    sum += src[c];
+  T run_ = (T)wg_excl_scan((int)sum, wtot);
+  int total = 0;
+  for (int j = 0; j < 16; j++)
+    total += wtot[j];
+  for (uint32_t c = c0; c < c1; c++)
+  {
+    const T m = src[c];
+    dst[c] = run_;
+    run_ += m;
+  }
+  wg_sync();
+  return (T)total;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the skeleton
+// A lane's sub-sequence: the bytes [s, end) are cut into sub-sequences of sb bytes, lane i of the workgroup on the i-th.  An interval
+// (sb = max(8, ceil(n / kThreads)), end = its trimmed end) over one workgroup, or an unmarked scan's chunk (kSubBytes, end = the scan's).
+struct SubLane
+{
+  uint64_t s0, end; // this lane's first byte, the end of the data
+  uint64_t E;       // the next sub-sequence's first byte (UINT64_MAX: none)
+  uint64_t cap;     // bound of the decode loop: every trip consumes a bit
+  uint32_t nact;    // lanes of the workgroup with data (at least 1)
+  bool active, first; // first: the lane's start is exact, not a guess (first0: lane 0's is)
+};
+
+__device__ __forceinline__ SubLane sub_lane(uint64_t s, uint64_t end, uint64_t sb, int tid, bool first0)
+{
+  SubLane q;
+  const uint64_t n = end > s ? end - s : 0, lanes = (n + sb - 1) / sb;
+  q.nact = n ? (uint32_t)(lanes < (uint64_t)kThreads ? lanes : (uint64_t)kThreads) : 1u;
+  q.active = (uint32_t)tid < q.nact;
+  q.s0 = s + (uint64_t)tid * sb;
+  q.end = end;
+  q.E = q.s0 + sb < end ? q.s0 + sb : ~uint64_t(0);
+  q.cap = 8 * (end - (q.s0 < end ? q.s0 : end)) + 64;
+  q.first = first0 && tid == 0;
+  return q;
+}
+
+// the tables and the blocks' components into LDS (lcomp: 16 words); the caller synchronises
+__device__ __forceinline__ void load_tables(const DecArgs &a, DevTables &T, uint32_t *lcomp, int tid)
+{
+  const uint32_t *src = (const uint32_t *)a.tab;
+  uint32_t *dst = (uint32_t *)&T;
+  for (int i = tid; i < (int)(sizeof(DevTables) / 4); i += kThreads)
+    dst[i] = src[i];
+  if (tid < 16)
+    lcomp[tid] = tid < (int)a.g.upm ? a.g.bcomp[tid] : 0;
+}
+
+// One speculating decode of the lane's sub-sequence from state `start`; a lane without data publishes no usable exit, no blocks, no DC.
+// The first pass starts every lane from 0: bit 0 of its first byte, the DC code of an MCU's first block.
+__device__ __forceinline__ void speculate(const DecArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t start, Lane &L)
+{
+  Reader r;
+  int dummy[3] = {0, 0, 0};
+  L.state = kErr;
+  L.blocks = L.dc[0] = L.dc[1] = L.dc[2] = 0;
+  if (!q.active)
+    return;
+  reader_init(r, a, q.s0, q.end, q.E, q.first);
+  run<false>(r, a, T, lcomp, start, L, 0, 0, 0, dummy, q.cap);
+}
+
+// The synchronisation inside a workgroup: lane 0 wants want0, lane i the exit of lane i - 1; a lane whose start differs decodes again,
+// until no start changes (at most nact + 1 trips: each trip makes one more lane exact).  exit_state: kThreads words of LDS, every
+// lane's exit state on return.  Returns whether this lane decoded again.
+__device__ __forceinline__ bool settle(const DecArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t want0,
+                                       uint32_t &my_start, Lane &L, uint32_t *exit_state)
+{
+  bool ran = false;
+  exit_state[threadIdx.x] = L.state;
+  for (uint32_t round = 0; round <= q.nact; round++)
+  {
+    wg_sync();
+    const uint32_t want = threadIdx.x == 0 ? want0 : exit_state[threadIdx.x - 1];
+    const bool changed = q.active && want != my_start;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (!__syncthreads_or(changed))
+      break;
+    if (changed)
+    {
+      my_start = want;
+      speculate(a, T, lcomp, q, my_start, L);
+      exit_state[threadIdx.x] = L.state;
+      ran = true;
+    }
+  }
+  wg_sync();
+  return ran;
+}
+
+// The write pass of a lane with data: the exact decode from `start`, unit0 blocks and the predictors `pred` before it, writing levels.
+// A decode error goes to *first_err (LDS, kNone before) as lane << 8 | code, the smallest winning; the status after the range's last
+// block to *fin.  Returns the unit the lane stopped in (unit0 + the blocks it completed): the failing one in the lane that wins.
+__device__ __forceinline__ uint32_t write_pass(const DecArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t start,
+                                               uint32_t unit0, uint32_t units, uint32_t mcu0, int pred[3], uint32_t *first_err, uint32_t *fin)
+{
+  Reader r;
+  Lane F;
+  reader_init(r, a, q.s0, q.end, q.E, q.first);
+  run<true>(r, a, T, lcomp, start, F, unit0, units, mcu0, pred, q.cap);
+  if (F.err && unit0 < units)
+    atomicMin(first_err, ((uint32_t)threadIdx.x << 8) | F.err);
+  if (F.finished)
+    *fin = F.fin;
+  return unit0 + (uint32_t)F.blocks;
+}
+
 } // namespace jpegdec
 } // namespace mdct
 
@@ -420,7 +523,22 @@ struct mdct_jpegdec_tables
   bool present[4];
 };
 
-// host: the descriptor's components (n_components and a non-empty MCU grid checked by the caller): sampling, slots, planes, block count
+// host: a scan descriptor's head for the decoder of scans with restart markers (marked: restart_interval > 0) or without
+// (restart_interval 0); wrong_kind: the caller's message for the other kind, which may print restart_interval (%zu)
+static int check_scan_head(const mdct_jpegdec_scan *d, bool marked, const char *wrong_kind)
+{
+  if (!d)
+    return fail(MDCT_INVALID_PARAMETER, "null scan descriptor");
+  if (d->n_components < 1 || d->n_components > MDCT_JPEGDEC_MAX_COMPONENTS)
+    return fail(MDCT_INVALID_PARAMETER, "%d components (1..3)", d->n_components);
+  if (!marked && (d->mcus_x == 0 || d->mcus_y == 0))
+    return fail(MDCT_INVALID_PARAMETER, "empty MCU grid");
+  if (d->mcus_x == 0 || d->mcus_y == 0 || marked != (d->restart_interval != 0))
+    return fail(MDCT_INVALID_PARAMETER, wrong_kind, d->restart_interval);
+  return MDCT_SUCCESS;
+}
+
+// host: ... and its components (after the head): sampling, slots, planes, block count
 static int check_components(const mdct_jpegdec_scan *d)
 {
   int upm = 0;
@@ -457,22 +575,22 @@ static int fill_geometry(const mdct_jpegdec_scan *desc, const mdct_jpegdec_table
     const mdct_jpegdec_component &q = desc->comp[c];
     if (!tables->present[q.dc_slot] || !tables->present[q.ac_slot])
       return fail(MDCT_INVALID_PARAMETER, "component %d uses an empty table slot (%d / %d)", c, q.dc_slot, q.ac_slot);
-    a.plane[c] = q.coef;
-    a.pitch[c] = q.pitch;
-    a.ch[c] = (uint32_t)q.h;
-    a.cv[c] = (uint32_t)q.v;
+    a.g.plane[c] = q.coef;
+    a.g.pitch[c] = q.pitch;
+    a.g.ch[c] = (uint32_t)q.h;
+    a.g.cv[c] = (uint32_t)q.v;
     for (int v = 0; v < q.v; v++) // T.81 A.2.3: a component's blocks in the MCU, left to right, top to bottom
       for (int h = 0; h < q.h; h++, b++)
       {
-        a.bcomp[b] = (uint8_t)c;
-        a.bh[b] = (uint8_t)h;
-        a.bv[b] = (uint8_t)v;
+        a.g.bcomp[b] = (uint8_t)c;
+        a.g.bh[b] = (uint8_t)h;
+        a.g.bv[b] = (uint8_t)v;
         a.bdc[b] = (uint8_t)q.dc_slot;
         a.bac[b] = (uint8_t)q.ac_slot;
       }
   }
-  a.upm = b;
-  a.mcus_x = (uint32_t)desc->mcus_x;
+  a.g.upm = b;
+  a.g.mcus_x = (uint32_t)desc->mcus_x;
   a.total_mcus = (uint32_t)(desc->mcus_x * desc->mcus_y);
   return MDCT_SUCCESS;
 }

@@ -316,26 +316,10 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
             specs, desc = scan_plan(info, si, sc, geo, grid, coefs)
             tables = Tables(specs)
             seg = torch.frombuffer(bytearray(raw[sc["start"]:sc["end"]]) or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
-            L = sc["end"] - sc["start"]
-            if sc["restart_interval"] == 0:
-                st = _decode_unmarked_scan(torch, desc, tables, seg, L, dev, stream)
+            try:
+                decode_scan(torch, si, sc, desc, tables, seg, dev, stream)
+            finally:
                 tables.close()
-                if st[0] != 0:
-                    raise JpegDecodeError(f"scan {si} (no restart markers): {_jpegdec_unmarked_lib.STATUS_NAMES.get(int(st[0]), int(st[0]))} "
-                                          f"after {int(st[1])} blocks", scan=si, status=st)
-                continue
-            n = n_intervals(desc)
-            off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            status = torch.empty(n, dtype=torch.int32, device=dev)
-            index(seg, n, off, status, scan_len=L, stream=stream)
-            decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
-            st = status.cpu().numpy()
-            tables.close()
-            bad = np.flatnonzero(st)
-            if bad.size:
-                k = int(bad[0])
-                raise JpegDecodeError(f"scan {si}: {bad.size} of {n} restart intervals failed; interval {k}: "
-                                      f"{_jpegdec_lib.STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
         if scale_denom != 1:
             out = scaled_planes(info, coefs, scale_denom, stream=stream, replicate=mode == "RGB")
             if mode == "RGB":
@@ -400,18 +384,37 @@ def to_rgb(planes, sampling, width, height, colour="YCbCr", layout="HWC", out=No
     return out
 
 
-def _decode_unmarked_scan(torch, desc, tables, seg, L, dev, stream):
-    """one scan without restart markers -> its status [code, blocks]; a NOT_SYNCHRONISED result (an ordinary status, not a fault) is
-    decoded once more with one fix round per chunk, which always converges"""
-    nbytes = unmarked_workspace(desc, L)
-    if nbytes == 0:
-        raise api.MdctError(f"invalid scan descriptor: {unmarked_last_error()}")
-    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # the caching allocator's blocks are 512-byte aligned
-    status = torch.empty(2, dtype=torch.int32, device=dev)
-    decode_unmarked(desc, tables, seg, work, status, scan_len=L, stream=stream)
-    st = status.cpu().numpy()
-    if st[0] == _jpegdec_unmarked_lib.NOT_SYNCHRONISED:
-        rounds = max(1, _ceil(L, _jpegdec_unmarked_lib.CHUNK_BYTES))
-        decode_unmarked(desc, tables, seg, work, status, scan_len=L, sync_rounds=rounds, stream=stream)
+def decode_scan(torch, si, sc, desc, tables, seg, dev, stream=None):
+    """decode scan si of read_jpeg's list as scan_plan planned it (seg: its bytes on the device) into the planes its descriptor names,
+    by the route its restart interval asks for, and wait for its status: per interval (restart-marked), or [code, blocks decoded]
+    (no markers; a NOT_SYNCHRONISED result, an ordinary status and not a fault, is decoded once more with one fix round per chunk,
+    which always converges).  Returns the status; JpegDecodeError for a scan that did not decode cleanly."""
+    L = sc["end"] - sc["start"]
+    if sc["restart_interval"] == 0:
+        nbytes = unmarked_workspace(desc, L)
+        if nbytes == 0:
+            raise api.MdctError(f"invalid scan descriptor: {unmarked_last_error()}")
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # the caching allocator's blocks are 512-byte aligned
+        status = torch.empty(2, dtype=torch.int32, device=dev)
+        decode_unmarked(desc, tables, seg, work, status, scan_len=L, stream=stream)
         st = status.cpu().numpy()
+        if st[0] == _jpegdec_unmarked_lib.NOT_SYNCHRONISED:
+            rounds = max(1, _ceil(L, _jpegdec_unmarked_lib.CHUNK_BYTES))
+            decode_unmarked(desc, tables, seg, work, status, scan_len=L, sync_rounds=rounds, stream=stream)
+            st = status.cpu().numpy()
+        if st[0] != 0:
+            raise JpegDecodeError(f"scan {si} (no restart markers): {_jpegdec_unmarked_lib.STATUS_NAMES.get(int(st[0]), int(st[0]))} "
+                                  f"after {int(st[1])} blocks", scan=si, status=st)
+        return st
+    n = n_intervals(desc)
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    index(seg, n, off, status, scan_len=L, stream=stream)
+    decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
+    st = status.cpu().numpy()
+    bad = np.flatnonzero(st)
+    if bad.size:
+        k = int(bad[0])
+        raise JpegDecodeError(f"scan {si}: {bad.size} of {n} restart intervals failed; interval {k}: "
+                              f"{_jpegdec_lib.STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
     return st

@@ -1,7 +1,8 @@
 """The GPU JPEG decoder (libmdct_jpegdec.so, include/mdct_jpegdec.h, simd_dct_amd/jpeg_decode.py) and the file reader
 jfif.read_jpeg.
 
-CPU: the reader on the engine's own files and on Pillow's, its refusals, the table validation, and the independent CPU checker
+CPU: the reader on the engine's own files and on Pillow's, its refusals, the table validation (and the decoders' host-compilable
+headers in a stand-alone program under sanitizers: tests/jpegdec_host_driver.cpp), and the independent CPU checker
 (tests/jpeg_decode_checker.py) anchored twice -- against the encoder's CPU checker (the levels the scans were made from) and against
 libjpeg (Pillow's decode of the same files, within the +-1 of two IDCTs).
 GPU: the engine's own scans decode to exactly the coefficients and pixels the encoder side computes; Pillow's files decode to exactly
@@ -168,6 +169,64 @@ def test_table_validation_without_device():
     assert D.tables_check([(many, list(range(12)) * 21 + [0] * 5), None, None, None]) == 1  # 257 values
     assert D.tables_check([(_specs()[0][0], _specs()[0][1][:-1]), None, None, None]) == 1  # counts and values disagree
     assert D.tables_check([(_specs()[2][0], [12] + _specs()[0][1][1:]), None, None, None]) == 1  # DC category 12
+
+
+def _counts(length, n):
+    bits = [0] * 16
+    bits[length - 1] = n
+    return bits
+
+
+# slot, (bits16, vals): what build_tables (csrc/huff_tables.h) refuses, the over-subscribed ones before it writes anything for the length
+REFUSED_SPECS = {
+    "three 1-bit codes": (0, (_counts(1, 3), [0, 0, 0])),
+    "255 1-bit codes": (2, (_counts(1, 255), [1] * 255)),
+    "five 2-bit codes": (1, (_counts(2, 5), [0] * 5)),
+    "an all-ones code": (3, ([1, 2] + [0] * 14, [0, 1, 2])),
+    "257 values": (2, (_counts(8, 255), [0] * 257)),
+    "counts that disagree with the values": (0, (_counts(2, 2), [0, 1, 2])),
+    "DC category 12": (0, (_counts(4, 1), [12])),
+    "AC size 11": (2, (_counts(4, 1), [0x0B])),
+}
+
+
+@pytest.mark.parametrize("case", sorted(REFUSED_SPECS))
+def test_tables_create_refuses_what_tables_check_refuses(case):
+    """mdct_jpegdec_tables_create builds into a real table struct where mdct_jpegdec_tables_check only validates: the same code and
+    message, no handle, and all of it before the first HIP call (so without a device)"""
+    import ctypes
+
+    from simd_dct_amd import _jpegdec_lib
+    from simd_dct_amd import jpeg_decode as D
+    slot, spec = REFUSED_SPECS[case]
+    specs = [spec if t == slot else None for t in range(4)]
+    rc = D.tables_check(specs)
+    message = D.last_error()
+    assert rc == 1 and f"slot {slot}: " in message, (rc, message)
+    b, v, n, keep = D._spec_arrays(specs)
+    handle = ctypes.c_void_p(0xDEAD)
+    assert _jpegdec_lib.load().mdct_jpegdec_tables_create(ctypes.byref(handle), b, v, n) == rc
+    assert D.last_error() == message
+    assert handle.value is None
+
+
+def test_host_pieces_under_sanitizers(tmp_path):
+    """csrc/huff_tables.h (build_tables writing a real DevTables: every code of the tables it accepts, the specifications it refuses,
+    nothing written outside the struct) and csrc/block_place.h (the place of every block of five MCU layouts against T.81 A.2.3, the
+    loop that zeroes a range of blocks) as tests/jpegdec_host_driver.cpp checks them: a stand-alone program, sanitizers linked in"""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "jpegdec_host"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "simd_dct_amd", "csrc"), os.path.join(ROOT, "tests", "jpegdec_host_driver.cpp"),
+                        "-o", str(exe)], capture_output=True, text=True)
+    if r.returncode != 0 and "san" in (r.stderr + r.stdout).lower() and "cannot find" in (r.stderr + r.stdout).lower():
+        pytest.skip("sanitizer runtime not installed: " + r.stderr[-200:])
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "jpegdec host ok" in r.stdout, r.stdout + r.stderr
 
 
 # ------------------------------------------------------------------------------------------ CPU: the checker, anchored twice

@@ -26,14 +26,8 @@ def prepare(torch, D, jfif, data):
     geo, grid = D.geometry(info)
     coefs = [torch.empty((by * 8, bx * 8), dtype=torch.int16, device="cuda") for _, _, bx, by in geo]
     calls, works = [], []
-    for sc in info["scans"]:
-        mcus_x, mcus_y, members = D.scan_geometry(info, sc, geo, grid)
-        specs, planes = [None] * 4, []
-        for c, (ci, h, v) in zip(sc["components"], members):
-            specs[c["td"]] = sc["huffman"][(0, c["td"])]
-            specs[2 + c["ta"]] = sc["huffman"][(1, c["ta"])]
-            planes.append((coefs[ci], geo[ci][2], geo[ci][3], h, v, c["td"], 2 + c["ta"]))
-        desc = D.scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"])
+    for si, sc in enumerate(info["scans"]):
+        specs, desc = D.scan_plan(info, si, sc, geo, grid, coefs)
         tab = D.Tables(specs)
         seg = torch.frombuffer(bytearray(data[sc["start"]:sc["end"]]), dtype=torch.uint8).cuda()
         if sc["restart_interval"] == 0:
