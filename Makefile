@@ -1,6 +1,6 @@
 # Top-level build for C/C++ users (the Python entry point __graft_entry__.build() does the same).
 #   make            libmdct_hip.so + the C++ CLI + the CPU checker
-#   make lib | cli | jpeg_example | oracle | ref | clean
+#   make lib | cli | jpeg_example | jpegcoef | oracle | ref | clean
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := simd_dct_amd/csrc
@@ -28,6 +28,15 @@ jpeg_example: tools/mdct_jpeg
 tools/mdct_jpeg: tools/mdct_jpeg.c include/mdct.h
 	gcc -O2 -std=c99 -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude $< -Lsimd_dct_amd -lmdct_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../simd_dct_amd' -Wl,-rpath,/opt/rocm/lib -o $@
 
+# JPEG in the coefficient domain (include/mdct_jpegcoef.h), with the library of the table-taking coders it links against; the other JPEG
+# stages are built by __graft_entry__.build() (its JPEG_LIBS table)
+SCAN_DEPS := $(wildcard $(CSRC)/*.h) $(CSRC)/mdct_kernels.hip include/mdct.h include/mdct_jpegenc_scan.h include/mdct_jpegenc_opt.h
+jpegcoef: simd_dct_amd/libmdct_jpegcoef.so
+simd_dct_amd/libmdct_jpegenc_opt.so: $(CSRC)/jpeg_encode_opt.hip $(SCAN_DEPS) $(LIB)
+	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
+simd_dct_amd/libmdct_jpegcoef.so: $(CSRC)/jpeg_coef.hip include/mdct_jpegcoef.h $(SCAN_DEPS) simd_dct_amd/libmdct_jpegenc_opt.so
+	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_jpegenc_opt -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
+
 oracle:
 	$(MAKE) -C oracle
 ref:
@@ -37,4 +46,4 @@ clean:
 	rm -f $(LIB) tools/simd_dct_cli tools/mdct_jpeg
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib cli jpeg_example oracle ref clean
+.PHONY: all lib cli jpeg_example jpegcoef oracle ref clean

@@ -8,8 +8,9 @@
 //
 // One kernel template, k_opt<H, V, STATS>, on the chunk skeleton it shares with k_scan_rows (scan_chunks.h; layouts and scan order:
 // scan_order.h): one workgroup per restart interval, the interval worked through in chunks, a chunk in a transform phase and a symbols
-// phase separated by a barrier.  This kernel's own are the LDS, the table / ring / histogram set-up, the symbols phase and the
-// epilogue.  The host checks it shares with jpeg_encode_scan.hip are scan_host.h's.
+// phase separated by a barrier.  The kernel's body -- the LDS, the table / ring / histogram set-up, the symbols phase and the epilogue --
+// is opt_symbols.h's, shared with k_coef (jpeg_coef.hip), whose levels come from a coefficient plane; here the source is ScanChunks
+// (pixels).  The host checks it shares with jpeg_encode_scan.hip and jpeg_coef.hip are scan_host.h's.
 // <H, V> is the luma sampling of an interleaved scan (<2, 2>, <2, 1>, <1, 1>; 3 / 2 / 3 waves) or <0, 0>: ONE plane, interval = one block
 // row, 4 waves, chunks of 256 blocks, scan order = lane order.
 // STATS = false: the symbols phase is HuffSeqCoder16 with the caller's tables.  Unless the host found the tables complete, a walk
@@ -29,6 +30,7 @@
 #include "launch_tally.h"
 #include "mdct_jpegenc_opt.h"
 #include "scan_chunks.h"
+#include "opt_symbols.h"
 #include "scan_host.h"
 #include "wg_sync.h"
 
@@ -39,9 +41,7 @@ namespace mdct
 namespace jpegenc_opt
 {
 
-constexpr uint32_t kRing = 1024;                        // words of bit stream held in LDS (as k_scan_rows)
-constexpr uint32_t kClass = MDCT_JPEGENC_OPT_HIST_CLASS; // counts per class
-constexpr uint32_t kHist = 2 * kClass;
+static_assert(opt_symbols::kClass == MDCT_JPEGENC_OPT_HIST_CLASS, "counts per class");
 
 struct OptArgs
 {
@@ -64,152 +64,12 @@ struct OptArgs
 static_assert(sizeof(OptArgs) <= 4096, "kernel argument block");
 
 using namespace scan_order;
-
-// SSSS of a DC difference as huff_dc_token codes it
-__device__ __forceinline__ uint32_t dc_category(int diff)
-{
-  diff = diff > 2047 ? 2047 : (diff < -2047 ? -2047 : diff);
-  return diff ? 32u - (uint32_t)__builtin_clz((uint32_t)(diff < 0 ? -diff : diff)) : 0u;
-}
-
-// RRRRSSSS of a 16-bit entry run << 12 | level as huff_ac_token12 codes it (0xF0 for the ZRL entry)
-__device__ __forceinline__ uint32_t ac_symbol12(uint32_t e)
-{
-  int l;
-  asm("v_bfe_i32 %0, %1, 0, 12" : "=v"(l) : "v"(e));
-  const int amp = l + (l >> 31);
-  int lead;
-  asm("v_ffbh_i32 %0, %1" : "=v"(lead) : "v"(amp));
-  const int s = l ? 32 - lead : 0;
-  return ((e >> 12) << 4) | (uint32_t)s;
-}
+using opt_symbols::kHist;
 
 template <int H, int V, bool STATS>
 __global__ __launch_bounds__((64 * kWaves<H, V>)) void k_opt(OptArgs a)
 {
-  using Chunks = ScanChunks<H, V, OptArgs>;
-  constexpr int WAVES = kWaves<H, V>;
-  constexpr uint32_t kThreads = Chunks::kThreads, M = Chunks::M;
-  __shared__ uint32_t ac[STATS ? 1 : 2][256], dc[STATS ? 1 : 2][12];
-  __shared__ __attribute__((aligned(16))) uint16_t rec_all[kThreads * kRec16Row];
-  __shared__ uint32_t meta[2][kThreads]; // by slot; [chunk parity] (ScanChunks)
-  __shared__ uint32_t ring[STATS ? 1 : kRing];
-  __shared__ uint32_t tot[2][WAVES];
-  __shared__ uint32_t ff_total;
-  __shared__ uint32_t hist[STATS ? WAVES : 1][STATS ? kHist : 1]; // one histogram per wave
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t my = a.my0 + blockIdx.x;
-  HuffSeqCoder16<WAVES, kRing> coder;
-  if constexpr (STATS)
-  {
-    for (uint32_t i = tid; i < WAVES * kHist; i += kThreads)
-      (&hist[0][0])[i] = 0;
-  }
-  else
-  {
-    for (uint32_t i = tid; i < 512; i += kThreads)
-      (&ac[0][0])[i] = (&a.ac[0][0])[i];
-    if (tid < 24)
-      (&dc[0][0])[tid] = (&a.dc[0][0])[tid];
-    if (tid == 0)
-      ff_total = 0;
-    for (uint32_t w = tid; w < kRing; w += kThreads)
-      ring[w] = 0;
-    coder.ring = ring;
-    coder.tot = tot;
-    coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)my * a.seg_stride);
-  }
-  Chunks chunks(a);
-  chunks.init(tid, lane, wave, my, rec_all, meta);
-
-  // ---- the symbols phase's block of this thread
-  const SeqBlock sb = seq_block<H, V>(tid);
-  const uint16_t *crec = rec_all + sb.slot * kRec16Row;
-  const bool cls = H == 0 ? a.cls0 != 0 : sb.chroma;                       // the block's class in the histogram
-  const uint32_t *cac = ac[(!STATS && sb.chroma) ? 1 : 0], *cdc = dc[(!STATS && sb.chroma) ? 1 : 0];
-  const unsigned long long cls_mask = __ballot(cls);                       // the wave's chroma lanes
-  uint32_t *whist = hist[STATS ? wave : 0];
-  uint32_t par = 0, uncoded = 0;
-  wg_sync(); // tables and the cleared ring / histograms
-  for (uint32_t m0 = 0, chunk = 0; m0 < a.mcus_x; m0 += M, chunk++)
-  {
-    chunks.transform(m0, chunk, par);
-    wg_sync(); // every block of the chunk is in LDS
-    const ChunkBlock b = chunks.block(sb, m0, par);
-    const bool live = b.live, blk_eob = b.eob;
-    const int blk_dc = b.dc, pred = b.pred, blk_n = live ? b.n : 0;
-    if constexpr (STATS)
-    {
-      uint32_t *h = whist + (cls ? kClass : 0u);
-      if (live)
-        atomicAdd(&h[dc_category(blk_dc - pred)], 1u);
-      // a symbol that many lanes hold at once: one add per class and wave
-      auto add_ballot = [&](bool p, uint32_t sym) {
-        const unsigned long long m = __ballot(p);
-        const uint32_t nl = (uint32_t)__popcll(m & ~cls_mask), nc = (uint32_t)__popcll(m & cls_mask);
-        if (lane == 0)
-        {
-          if (nl)
-            atomicAdd(&whist[16 + sym], nl);
-          if (nc)
-            atomicAdd(&whist[kClass + 16 + sym], nc);
-        }
-      };
-      add_ballot(live && blk_eob, 0x00u);
-      for (int i = 0; __ballot(i < blk_n) != 0; i++)
-      { // the lanes' i-th entries together
-        const bool on = i < blk_n;
-        const uint32_t sym = on ? ac_symbol12(crec[i]) : 0xFFFFu;
-        add_ballot(sym == 0x01u, 0x01u);
-        add_ballot(sym == 0x02u, 0x02u);
-        add_ballot(sym == 0x11u, 0x11u);
-        if (on && sym != 0x01u && sym != 0x02u && sym != 0x11u)
-          atomicAdd(&h[16 + sym], 1u);
-      }
-      wg_sync(); // every row of the chunk has been walked: the next chunk's transform may write them (the coder's last barrier)
-    }
-    else
-    {
-      if (!a.complete && live)
-      { // the symbols this block needs that the tables do not code
-        uncoded += (cdc[dc_category(blk_dc - pred)] >> 16) == 0 ? 1u : 0u;
-        for (int i = 0; i < blk_n; i++)
-          uncoded += (cac[ac_symbol12(crec[i])] >> 16) == 0 ? 1u : 0u;
-        if (blk_eob)
-          uncoded += (cac[0x00] >> 16) == 0 ? 1u : 0u;
-      }
-      coder.chunk(crec, blk_n, live, blk_dc, pred, blk_eob, cac, cdc);
-    }
-    par ^= 1;
-  }
-  if constexpr (STATS)
-  {
-    wg_sync();
-    for (uint32_t i = tid; i < kHist; i += kThreads)
-    {
-      uint32_t s = 0;
-#pragma unroll
-      for (int w = 0; w < WAVES; w++)
-        s += hist[w][i];
-      if (s)
-        atomicAdd(&a.hist[i], s);
-    }
-  }
-  else
-  {
-    if (coder.ff)
-      atomicAdd(&ff_total, coder.ff);
-    if (uncoded)
-      atomicAdd(a.uncoded, uncoded);
-    wg_sync();
-    if (tid == 0)
-    {
-      uint32_t ff_last;
-      a.seg_bytes[my] = coder.finish(&ff_last);
-      a.ff_counts[my] = ff_total + ff_last;
-    }
-  }
+  opt_symbols::opt_kernel_body<ScanChunks<H, V, OptArgs>, H, V, STATS>(a);
 }
 
 } // namespace jpegenc_opt
@@ -219,56 +79,6 @@ using namespace mdct::jpegenc_opt;
 
 namespace
 {
-
-// a specification -> size << 16 | code per symbol (T.81 Annex C); checked as mdct_jpegdec_tables_check checks one, and no symbol twice.
-// complete: every baseline symbol of the class has a code.
-int spec_codes(const mdct_jpegenc_opt_spec *sp, bool is_ac, const char *name, uint32_t *tab, bool *complete)
-{
-  const int cap = is_ac ? 256 : 12;
-  memset(tab, 0, sizeof(uint32_t) * (size_t)cap);
-  if (!sp || !sp->bits16 || !sp->vals)
-    return fail(MDCT_INVALID_PARAMETER, "%s: null specification / counts / values", name);
-  if (sp->nvals < 1 || sp->nvals > 256)
-    return fail(MDCT_INVALID_PARAMETER, "%s: %d values (1..256)", name, sp->nvals);
-  int total = 0;
-  for (int l = 0; l < 16; l++)
-    total += sp->bits16[l];
-  if (total != sp->nvals)
-    return fail(MDCT_INVALID_PARAMETER, "%s: the 16 counts add up to %d codes, %d values given", name, total, sp->nvals);
-  uint32_t code = 0;
-  bool seen[256] = {false};
-  for (uint32_t l = 1, p = 0; l <= 16; l++)
-  {
-    const uint32_t n = sp->bits16[l - 1];
-    for (uint32_t i = 0; i < n; i++, p++)
-    {
-      const int v = sp->vals[p];
-      if (is_ac ? (v & 15) > 10 : v > 11)
-        return fail(MDCT_INVALID_PARAMETER, "%s: value 0x%02x is not a baseline %s symbol", name, v, is_ac ? "AC" : "DC");
-      if (seen[v])
-        return fail(MDCT_INVALID_PARAMETER, "%s: value 0x%02x is named twice", name, v);
-      seen[v] = true;
-    }
-    code += n;
-    if (code >= (1u << l)) // no code may be all 1-bits, as libjpeg requires
-      return fail(MDCT_INVALID_PARAMETER, "%s: codes over-subscribed at length %u", name, l);
-    code <<= 1;
-  }
-  annex_c_codes(sp->bits16, sp->vals, sp->nvals, cap, tab);
-  bool all = true;
-  if (is_ac)
-  {
-    all = tab[0x00] && tab[0xF0];
-    for (int r = 0; r < 16; r++)
-      for (int s = 1; s <= 10; s++)
-        all = all && tab[r << 4 | s];
-  }
-  else
-    for (int s = 0; s < 12; s++)
-      all = all && tab[s];
-  *complete = *complete && all;
-  return MDCT_SUCCESS;
-}
 
 void common_args(OptArgs &a)
 {

@@ -1,6 +1,6 @@
-// scan_chunks.h -- the chunk skeleton of the JPEG scan coders: k_scan_rows (jpeg_encode_scan.hip) and k_opt (jpeg_encode_opt.hip)
-// work an MCU row (k_opt<0, 0>: a block row of one plane) through in chunks of kMcus MCUs = 64 * kWaves blocks, a chunk in two phases
-// separated by a barrier (layouts and scan order: scan_order.h) --
+// scan_chunks.h -- the chunk skeleton of the JPEG scan coders: k_scan_rows (jpeg_encode_scan.hip), k_opt (jpeg_encode_opt.hip) and
+// k_coef (jpeg_coef.hip) work an MCU row (<0, 0>: a block row of one plane) through in chunks of kMcus MCUs = 64 * kWaves blocks, a
+// chunk in two phases separated by a barrier (layouts and scan order: scan_order.h) --
 //   transform  lane = block, COMPONENT-UNIFORM waves, so the quantiser multipliers stay wave-uniform scalar operands read from the
 //              argument segment (two OwnTables, the wave picks one) and a wave's row loads are contiguous in one plane row.  Each lane
 //              leaves its block's AC entries in its LDS row and (DC, entry count, EOB flag) in meta[].  The next chunk's pixel rows
@@ -9,7 +9,9 @@
 //   symbols    thread s takes the s-th block of the chunk in scan order and reads the LDS row of the lane that transformed it; its
 //              DC predictor is the previous block of the same component: a plain LDS read (meta[] of this chunk, or of the previous
 //              chunk for the first block of a component -- meta is double-buffered --, or 0 at the row's start).
-// The transform phase and the read-out of a block are here; the symbols phase and the epilogue are each kernel's own.
+// ChunkGrid holds what does not depend on where the levels come from: which block a lane takes and the read-out of a block.  The
+// source is a class on top of it: ScanChunks here (pixels -> AAN -> quantiser), CoefChunks (coef_chunks.h: a fetch from a
+// coefficient plane).  The symbols phase and the epilogue are the kernels' (k_scan_rows its own, k_opt and k_coef: opt_symbols.h).
 // Include after aan_fwd.h and mdct_kernels.hip's MDCT_AAN_FWD_ONLY region.  Device code only.
 #pragma once
 #include "aan_fwd.h"
@@ -32,41 +34,28 @@ struct ChunkBlock
   bool eob;
 };
 
-// Args: the kernel's argument struct, with px[3], pitch[3], tb[2], consts, mcus_x and dc_shift (ScanArgs, OptArgs).  The kernel's own
-// type, not a common base: the multiplier pairs are read at offsetof(Args, tb) of the argument segment.
+// Args: the kernel's argument struct, with mcus_x.  The kernel's own type, not a common base: a source may read its tables at
+// offsetof(Args, ...) of the argument segment.
 template <int H, int V, class Args>
-struct ScanChunks
+struct ChunkGrid
 {
   static constexpr uint32_t kThreads = 64 * scan_order::kWaves<H, V>, M = scan_order::kMcus<H, V>;
   static_assert(kThreads == M * scan_order::kBlocksPerMcu<H, V>, "one symbols thread per block of the chunk");
 
   const Args &a;
   uint32_t tid, bx0, step, last_blk;
-  size_t pitch;
-  const uint8_t *src_row;
-  uint2 rows[8];
-  karg_pairs_t qf;
   uint16_t *rec;              // this lane's LDS row
   uint32_t (*meta)[kThreads]; // DC (low 16 bits) | entries << 16 | EOB needed << 24, by slot; [chunk parity]
 
-  __device__ __forceinline__ explicit ScanChunks(const Args &a_) : a(a_) {}
+  __device__ __forceinline__ explicit ChunkGrid(const Args &a_) : a(a_) {}
 
-  // the 8 rows of block min(bx, last) of the block row (lanes past the row's end redo the last block)
-  __device__ __forceinline__ void fetch(uint32_t bx)
-  {
-    const uint8_t *src = src_row + (size_t)min(bx, last_blk) * 8;
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-      rows[r] = load8(src + (size_t)r * pitch);
-  }
-
-  // the transform phase's block of this thread: plane, block row, first block and blocks per chunk; its first rows are requested
-  __device__ __forceinline__ void init(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[kThreads])
+  // the transform phase's block of this thread: component, block row of its plane, first block and blocks per chunk
+  __device__ __forceinline__ void place(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[kThreads], uint32_t &comp,
+                                        uint32_t &brow, bool &chroma_wave)
   {
     tid = tid_;
     meta = meta_;
-    const bool chroma_wave = H == 0 ? false : H == 1 ? wave > 0 : wave == (uint32_t)V;
-    uint32_t comp, brow;
+    chroma_wave = H == 0 ? false : H == 1 ? wave > 0 : wave == (uint32_t)V;
     if (H == 0)
     {
       comp = 0;
@@ -99,6 +88,67 @@ struct ScanChunks
       last_blk = a.mcus_x - 1;
       brow = my;
     }
+    rec = rec_all + tid * kRec16Row;
+  }
+
+  // the lane's entries and (DC, entry count, EOB flag) of this chunk, from its 64 levels (low 16 bits of val[], natural order)
+  __device__ __forceinline__ void leave(const uint32_t (&val)[64], uint32_t par)
+  {
+    int my_dc;
+    bool need_eob;
+    const uint32_t n = compact_levels16(val, rec, my_dc, need_eob);
+    meta[par][tid] = ((uint32_t)my_dc & 0xFFFFu) | n << 16 | (need_eob ? 1u << 24 : 0u);
+  }
+
+  // after the barrier: the block sb of the chunk at MCU m0, read out of meta
+  __device__ __forceinline__ ChunkBlock block(const scan_order::SeqBlock sb, uint32_t m0, uint32_t par) const
+  {
+    const uint32_t me = meta[par][sb.slot];
+    ChunkBlock b;
+    b.n = (int)((me >> 16) & 0xFFu);
+    b.live = m0 + sb.mcu < a.mcus_x;
+    b.dc = (int)(int16_t)(me & 0xFFFFu);
+    b.pred = sb.carry ? (m0 == 0 ? 0 : (int)(int16_t)(meta[par ^ 1][sb.pred] & 0xFFFFu)) : (int)(int16_t)(meta[par][sb.pred] & 0xFFFFu);
+    b.eob = (me >> 24) != 0;
+    return b;
+  }
+};
+
+// The pixel source.  Args: with px[3], pitch[3], tb[2], consts, mcus_x and dc_shift (ScanArgs, OptArgs); the multiplier pairs are read
+// at offsetof(Args, tb) of the argument segment.
+template <int H, int V, class Args>
+struct ScanChunks : ChunkGrid<H, V, Args>
+{
+  using Grid = ChunkGrid<H, V, Args>;
+  using Grid::a;
+  using Grid::bx0;
+  using Grid::last_blk;
+  using Grid::M;
+  using Grid::step;
+  static constexpr bool kCountsLoss = false; // the quantiser saturates: nothing to report
+
+  size_t pitch;
+  const uint8_t *src_row;
+  uint2 rows[8];
+  karg_pairs_t qf;
+
+  __device__ __forceinline__ explicit ScanChunks(const Args &a_) : Grid(a_) {}
+
+  // the 8 rows of block min(bx, last) of the block row (lanes past the row's end redo the last block)
+  __device__ __forceinline__ void fetch(uint32_t bx)
+  {
+    const uint8_t *src = src_row + (size_t)min(bx, last_blk) * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+      rows[r] = load8(src + (size_t)r * pitch);
+  }
+
+  // the transform phase's block of this thread (ChunkGrid::place) in its plane; its first rows are requested
+  __device__ __forceinline__ void init(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[Grid::kThreads])
+  {
+    uint32_t comp, brow;
+    bool chroma_wave;
+    Grid::place(tid_, lane, wave, my, rec_all, meta_, comp, brow, chroma_wave);
     // (selects, not an index: the argument block stays in scalar registers)
     const size_t pitch0 = a.pitch[0], pitch1 = a.pitch[1], pitch2 = a.pitch[2];
     const uint8_t *const px0 = a.px[0], *const px1 = a.px[1], *const px2 = a.px[2];
@@ -107,7 +157,6 @@ struct ScanChunks
     fetch(bx0);
     // the multiplier pairs of this wave's table (wave-uniform: scalar loads from the argument segment)
     qf = karg_pairs(offsetof(Args, tb) + (chroma_wave ? sizeof(OwnTables) : 0) + offsetof(OwnTables, qf));
-    rec = rec_all + tid * kRec16Row;
   }
 
   // chunk number `chunk`, at MCU m0 of the row: rows -> levels -> entries in the lane's LDS row and meta[par][tid]; then the next
@@ -127,25 +176,9 @@ struct ScanChunks
     }
     uint32_t val[64];
     fwd_v_quant_levels<true>(K, P, qf, a.dc_shift, val);
-    int my_dc;
-    bool need_eob;
-    const uint32_t n = compact_levels16(val, rec, my_dc, need_eob);
-    meta[par][tid] = ((uint32_t)my_dc & 0xFFFFu) | n << 16 | (need_eob ? 1u << 24 : 0u);
+    Grid::leave(val, par);
     if (m0 + M < a.mcus_x)
       fetch(bx0 + (chunk + 1) * step);
-  }
-
-  // after the barrier: the block sb of the chunk at MCU m0, read out of meta
-  __device__ __forceinline__ ChunkBlock block(const scan_order::SeqBlock sb, uint32_t m0, uint32_t par) const
-  {
-    const uint32_t me = meta[par][sb.slot];
-    ChunkBlock b;
-    b.n = (int)((me >> 16) & 0xFFu);
-    b.live = m0 + sb.mcu < a.mcus_x;
-    b.dc = (int)(int16_t)(me & 0xFFFFu);
-    b.pred = sb.carry ? (m0 == 0 ? 0 : (int)(int16_t)(meta[par ^ 1][sb.pred] & 0xFFFFu)) : (int)(int16_t)(meta[par][sb.pred] & 0xFFFFu);
-    b.eob = (me >> 24) != 0;
-    return b;
   }
 };
 

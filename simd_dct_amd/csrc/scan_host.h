@@ -3,7 +3,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
+#include "mdct_jpegenc_opt.h"
 #include "mdct_jpegenc_scan.h"
 #include "own_tables.h"
 
@@ -11,7 +13,7 @@ namespace
 {
 
 // the three planes of an interleaved scan: *h, *v the luma sampling, the MCU grid from the chroma planes
-int check_mcu_planes(const mdct_jpegenc_scan_plane *planes, int *h, int *v, size_t *mcus_x, size_t *mcus_y)
+[[maybe_unused]] int check_mcu_planes(const mdct_jpegenc_scan_plane *planes, int *h, int *v, size_t *mcus_x, size_t *mcus_y)
 {
   for (int c = 0; c < 3; c++)
     if (!planes[c].px)
@@ -49,7 +51,7 @@ int check_mcu_planes(const mdct_jpegenc_scan_plane *planes, int *h, int *v, size
 }
 
 // a quantisation table -> the multiplier tables of the forward path, in the pair order of the column pass
-int fill_lut(const float *lut, mdct::OwnTables &tb, const char *name)
+[[maybe_unused]] int fill_lut(const float *lut, mdct::OwnTables &tb, const char *name)
 {
   const int bad = mdct::own_tables_fill(lut, tb, /*pair_order=*/true);
   if (bad >= 0)
@@ -77,6 +79,56 @@ void annex_c_codes(const uint8_t *bits16, const uint8_t *vals, int nvals, int ca
     for (int i = 0; i < bits16[len - 1] && k < nvals; i++, k++, code++)
       if (vals[k] < cap)
         tab[vals[k]] = len << 16 | code;
+}
+
+// a specification -> size << 16 | code per symbol (T.81 Annex C); checked as mdct_jpegdec_tables_check checks one, and no symbol twice.
+// complete: every baseline symbol of the class has a code.
+[[maybe_unused]] int spec_codes(const mdct_jpegenc_opt_spec *sp, bool is_ac, const char *name, uint32_t *tab, bool *complete)
+{
+  const int cap = is_ac ? 256 : 12;
+  memset(tab, 0, sizeof(uint32_t) * (size_t)cap);
+  if (!sp || !sp->bits16 || !sp->vals)
+    return fail(MDCT_INVALID_PARAMETER, "%s: null specification / counts / values", name);
+  if (sp->nvals < 1 || sp->nvals > 256)
+    return fail(MDCT_INVALID_PARAMETER, "%s: %d values (1..256)", name, sp->nvals);
+  int total = 0;
+  for (int l = 0; l < 16; l++)
+    total += sp->bits16[l];
+  if (total != sp->nvals)
+    return fail(MDCT_INVALID_PARAMETER, "%s: the 16 counts add up to %d codes, %d values given", name, total, sp->nvals);
+  uint32_t code = 0;
+  bool seen[256] = {false};
+  for (uint32_t l = 1, p = 0; l <= 16; l++)
+  {
+    const uint32_t n = sp->bits16[l - 1];
+    for (uint32_t i = 0; i < n; i++, p++)
+    {
+      const int v = sp->vals[p];
+      if (is_ac ? (v & 15) > 10 : v > 11)
+        return fail(MDCT_INVALID_PARAMETER, "%s: value 0x%02x is not a baseline %s symbol", name, v, is_ac ? "AC" : "DC");
+      if (seen[v])
+        return fail(MDCT_INVALID_PARAMETER, "%s: value 0x%02x is named twice", name, v);
+      seen[v] = true;
+    }
+    code += n;
+    if (code >= (1u << l)) // no code may be all 1-bits, as libjpeg requires
+      return fail(MDCT_INVALID_PARAMETER, "%s: codes over-subscribed at length %u", name, l);
+    code <<= 1;
+  }
+  annex_c_codes(sp->bits16, sp->vals, sp->nvals, cap, tab);
+  bool all = true;
+  if (is_ac)
+  {
+    all = tab[0x00] && tab[0xF0];
+    for (int r = 0; r < 16; r++)
+      for (int s = 1; s <= 10; s++)
+        all = all && tab[r << 4 | s];
+  }
+  else
+    for (int s = 0; s < 12; s++)
+      all = all && tab[s];
+  *complete = *complete && all;
+  return MDCT_SUCCESS;
 }
 
 } // namespace

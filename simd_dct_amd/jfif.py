@@ -43,7 +43,7 @@ def scan_bytes(segments, seg_bytes, seg_stride):
     return b"".join(out)
 
 
-def write_jpeg(components, width, height, specs=None, sampling=None, interleaved=None):
+def write_jpeg(components, width, height, specs=None, sampling=None, interleaved=None, *, table_per_component=False, colorspace=None):
     """components: list of 1 (grey) or 3 (Y, Cb, Cr with Cb/Cr at half resolution) dicts with keys
          'blocks_per_row', 'qtable' (64 integers 1..255, natural order v*8+u) and either
          'scan' (bytes / uint8 array: the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it) or
@@ -56,13 +56,31 @@ def write_jpeg(components, width, height, specs=None, sampling=None, interleaved
          (T.81 A.2.3) replaces the per-component scans -- one DRI (= MCUs per row, the scan's restart interval), one SOS naming all
          three components (Y: tables 0/0, Cb and Cr: 1/1), the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it.  The
          components then need 'qtable' only.
+       table_per_component: False: two quantisation tables are written, the first component's as table 0 and the second's as table 1,
+         which the third shares.  True: every component's own 'qtable' is written; equal tables share an id, in order of appearance.
+       colorspace: None, 'grey' or 'YCbCr': a JFIF APP0; 'RGB' (three components that are R, G, B, not converted): an Adobe APP14 with
+         transform 0 and no APP0 -- read_jpeg reports it as 'RGB'.
        Returns the file as bytes."""
     specs = specs or {w: api.huffman_spec(w) for w in range(4)}
     zz = api.zigzag_table()
     nc = len(components)
     assert nc in (1, 3)
-    f = [b"\xff\xd8", _seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
-    qts = [components[0]["qtable"]] + ([components[1]["qtable"]] if nc == 3 else [])
+    if colorspace not in (None, "grey", "YCbCr", "RGB") or (colorspace == "grey") != (nc == 1 and colorspace is not None):
+        raise ValueError(f"colorspace {colorspace!r} for {nc} components (None; 'grey' for one; 'YCbCr' or 'RGB' for three)")
+    if colorspace == "RGB":
+        f = [b"\xff\xd8", _seg(0xEE, b"Adobe" + struct.pack(">HHHB", 100, 0, 0, 0))]
+    else:
+        f = [b"\xff\xd8", _seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    if table_per_component:
+        qts, tq_of = [], []
+        for c in components:
+            key = [int(x) for x in np.asarray(c["qtable"]).reshape(64)]
+            if key not in qts:
+                qts.append(key)
+            tq_of.append(qts.index(key))
+    else:
+        qts = [components[0]["qtable"]] + ([components[1]["qtable"]] if nc == 3 else [])
+        tq_of = [min(ci, 1) for ci in range(nc)]
     for tq, q in enumerate(qts):
         q = np.asarray(q).reshape(64)
         assert np.all(q == np.rint(q)) and q.min() >= 1 and q.max() <= 255, "baseline DQT holds 8-bit integers"
@@ -72,7 +90,7 @@ def write_jpeg(components, width, height, specs=None, sampling=None, interleaved
         sampling = [(1, 1)] if nc == 1 else [(2, 2), (1, 1), (1, 1)]
     assert len(sampling) == nc and all(1 <= h <= 4 and 1 <= v <= 4 for h, v in sampling), "sampling factors 1..4 per component"
     for ci, (h, v) in enumerate(sampling):
-        sof += bytes([ci + 1, (h << 4) | v, min(ci, 1)])
+        sof += bytes([ci + 1, (h << 4) | v, tq_of[ci]])
     f.append(_seg(0xC0, sof))
     f.append(_seg(0xC4, _dht(0, 0, *specs[0]) + _dht(1, 0, *specs[1]) + (_dht(0, 1, *specs[2]) + _dht(1, 1, *specs[3]) if nc == 3 else b"")))
     if interleaved is not None:

@@ -282,6 +282,34 @@ def scaled_planes(info, coefs, scale_denom, stream=None, replicate=False):
     return [p[:sg[2], :sg[1]] if r == (1, 1) else p[:sh, :sw] for p, sg, r in zip(px, sgeo, reps)]
 
 
+def decode_coefficients(data, device=None, stream=None, *, info=None):
+    """The front of decode_jpeg on its own: parse the file (jfif.read_jpeg), plan and entropy-decode every scan on the GPU.  No inverse
+    DCT runs.  -> (info, coefs): read_jpeg's dict and one quantised int16 coefficient plane per component on the device,
+    [blocks_y * 8, blocks_x * 8], padded to the MCU grid (geometry), not dequantised.  info: read_jpeg(data, require_restart=False) if
+    the caller has parsed the file already.  Raises as decode_jpeg does: jfif.JpegFormatError for a file outside the supported subset,
+    JpegDecodeError when a scan does not decode cleanly."""
+    import torch
+
+    if info is None:
+        info = jfif.read_jpeg(data, require_restart=False)
+    dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+    raw = bytes(data)
+    geo, grid = geometry(info)
+    # zeroed: a non-interleaved scan of a subsampled component covers its own block grid (T.81 A.2.2), which may be smaller than the
+    # plane padded to the MCU grid
+    coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
+    with torch.cuda.device(dev):
+        for si, sc in enumerate(info["scans"]):
+            specs, desc = scan_plan(info, si, sc, geo, grid, coefs)
+            tables = Tables(specs)
+            seg = torch.frombuffer(bytearray(raw[sc["start"]:sc["end"]]) or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
+            try:
+                decode_scan(torch, si, sc, desc, tables, seg, dev, stream)
+            finally:
+                tables.close()
+    return info, coefs
+
+
 def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None, layout="HWC", scale_denom=1):
     """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file).  Returns one uint8
     tensor [height, width] per component (cropped to its true size); with coefficients=True also the quantised int16 coefficient planes
@@ -306,20 +334,9 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
     if mode == "RGB":
         _colour_params(info)
     dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
-    raw = bytes(data)
-    geo, grid = geometry(info)
-    # zeroed: a non-interleaved scan of a subsampled component covers its own block grid (T.81 A.2.2), which may be smaller than the
-    # plane padded to the MCU grid
-    coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
+    geo, _ = geometry(info)
+    _, coefs = decode_coefficients(data, dev, stream, info=info)
     with torch.cuda.device(dev):
-        for si, sc in enumerate(info["scans"]):
-            specs, desc = scan_plan(info, si, sc, geo, grid, coefs)
-            tables = Tables(specs)
-            seg = torch.frombuffer(bytearray(raw[sc["start"]:sc["end"]]) or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
-            try:
-                decode_scan(torch, si, sc, desc, tables, seg, dev, stream)
-            finally:
-                tables.close()
         if scale_denom != 1:
             out = scaled_planes(info, coefs, scale_denom, stream=stream, replicate=mode == "RGB")
             if mode == "RGB":
