@@ -14,8 +14,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -ffp-contract=off -fno-slp-vectorize -mll
 
 all: lib cli oracle
 
+# every header is a dependency of every library: no list kept by hand, none to go stale (rebuilding everything takes under a minute)
+HEADERS := $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
+
 lib: $(LIB)
-$(LIB): $(CSRC)/shim_host.h $(CSRC)/mdct_kernels.hip $(CSRC)/mdct_api.hip $(CSRC)/shim.hip $(CSRC)/comm.hip $(CSRC)/stages.hip $(CSRC)/mdct_kernels.h $(CSRC)/scan_records.h $(CSRC)/huffman_rows.h $(CSRC)/pack_rows.h $(CSRC)/wg_sync.h $(CSRC)/batch_plan.h include/mdct.h include/simd_dct_shim.h
+$(LIB): $(CSRC)/mdct_kernels.hip $(CSRC)/mdct_api.hip $(CSRC)/shim.hip $(CSRC)/comm.hip $(CSRC)/stages.hip $(HEADERS)
 	$(HIPCC) $(HIPFLAGS) -shared $(CSRC)/mdct_kernels.hip $(CSRC)/mdct_api.hip $(CSRC)/shim.hip $(CSRC)/comm.hip $(CSRC)/stages.hip -ldl -o $@
 
 cli: tools/simd_dct_cli
@@ -30,11 +33,10 @@ tools/mdct_jpeg: tools/mdct_jpeg.c include/mdct.h
 
 # JPEG in the coefficient domain (include/mdct_jpegcoef.h), with the library of the table-taking coders it links against; the other JPEG
 # stages are built by __graft_entry__.build() (its JPEG_LIBS table)
-SCAN_DEPS := $(wildcard $(CSRC)/*.h) $(CSRC)/mdct_kernels.hip include/mdct.h include/mdct_jpegenc_scan.h include/mdct_jpegenc_opt.h
 jpegcoef: simd_dct_amd/libmdct_jpegcoef.so
-simd_dct_amd/libmdct_jpegenc_opt.so: $(CSRC)/jpeg_encode_opt.hip $(SCAN_DEPS) $(LIB)
+simd_dct_amd/libmdct_jpegenc_opt.so: $(CSRC)/jpeg_encode_opt.hip $(HEADERS) $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
-simd_dct_amd/libmdct_jpegcoef.so: $(CSRC)/jpeg_coef.hip include/mdct_jpegcoef.h $(SCAN_DEPS) simd_dct_amd/libmdct_jpegenc_opt.so
+simd_dct_amd/libmdct_jpegcoef.so: $(CSRC)/jpeg_coef.hip $(HEADERS) simd_dct_amd/libmdct_jpegenc_opt.so
 	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_jpegenc_opt -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
 
 oracle:

@@ -1,9 +1,8 @@
 // aan_fwd.h -- device pieces of the engine-own FORWARD path that more than one translation unit compiles: the packed-fp32 helpers,
 // the quantiser's constants, the 8-byte row load, the byte -> float convert, the constant pairs of the AAN passes and the scalar-load
-// views of a kernel's argument segment.  mdct_kernels.hip (libmdct_hip.so) includes it, and so do jpeg_encode_scan.hip
-// (libmdct_jpegenc_scan.so) and jpeg_encode_opt.hip (libmdct_jpegenc_opt.so), which then compile the forward AAN passes, the quantiser
-// and the zig-zag compaction out of mdct_kernels.hip itself (its MDCT_AAN_FWD_ONLY region) for the chunk skeleton they share
-// (scan_chunks.h): one text, the same coefficients by construction.  Device code only.
+// views of a kernel's argument segment.  Everything aan_passes.h -- the AAN passes, the quantiser and the zig-zag compaction that
+// mdct_kernels.hip (libmdct_hip.so) and the JPEG scan coders (jpeg_encode_scan.hip, jpeg_encode_opt.hip, jpeg_coef.hip: a library each)
+// all compile -- and the chunk skeleton of those coders (scan_chunks.h) are written in.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

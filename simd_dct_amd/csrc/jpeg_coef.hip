@@ -8,7 +8,7 @@
 // k_coef<H, V, STATS> is k_opt (jpeg_encode_opt.hip) with another source of levels: the kernel body -- LDS, set-up, symbols phase,
 // epilogue -- is opt_symbols.h's, the lane-to-block layout and the read-out of a block scan_chunks.h's ChunkGrid; this file's own is
 // CoefChunks, whose "transform" phase is a fetch: a lane loads its block's 8 rows as 8 loads of 16 bytes (a wave's loads of one row
-// are 1 KiB of consecutive plane), widens them into the val[64] that compact_levels16 (mdct_kernels.hip's MDCT_AAN_FWD_ONLY region)
+// are 1 KiB of consecutive plane), widens them into the val[64] that compact_levels16 (aan_passes.h)
 // reads, clamps AC levels to +-1023 and counts those it had to clamp, and requests the next chunk's rows before the barrier.
 //
 // k_coef_transform: one wave per tile of 8 x 8 blocks of dst.  The blocks of src that land in the tile are a tile of 8 x 8 blocks too
@@ -19,9 +19,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "aan_fwd.h"
-#define MDCT_AAN_FWD_ONLY
-#include "mdct_kernels.hip" // only its MDCT_AAN_FWD_ONLY region; of it, compact_levels16
+#include "aan_passes.h" // of it, compact_levels16
 #include "host_error.h"
 #include "launch_tally.h"
 #include "mdct_jpegcoef.h"

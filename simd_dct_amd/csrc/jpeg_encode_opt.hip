@@ -3,8 +3,8 @@
 // (DESIGN.md section 4.9.2).
 //
 // Built into its own library, libmdct_jpegenc_opt.so, linked against libmdct_hip.so (launch tally).  As in jpeg_encode_scan.hip the
-// coefficients are the engine's own: the forward passes, the quantiser and the zig-zag compaction are compiled from mdct_kernels.hip's
-// MDCT_AAN_FWD_ONLY region and the multiplier tables come from own_tables.h; the bits are written by HuffSeqCoder16 (huffman_rows.h).
+// coefficients are the engine's own: the forward passes, the quantiser and the zig-zag compaction are aan_passes.h's and the multiplier
+// tables come from own_tables.h; the bits are written by HuffSeqCoder16 (huffman_rows.h).
 //
 // One kernel template, k_opt<H, V, STATS>, on the chunk skeleton it shares with k_scan_rows (scan_chunks.h; layouts and scan order:
 // scan_order.h): one workgroup per restart interval, the interval worked through in chunks, a chunk in a transform phase and a symbols
@@ -23,9 +23,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "aan_fwd.h"
-#define MDCT_AAN_FWD_ONLY
-#include "mdct_kernels.hip" // only its MDCT_AAN_FWD_ONLY region: aan_fwd_h, aan_fwd_v, fwd_v_quant_levels, compact_levels16
+#include "aan_passes.h" // aan_fwd_h, aan_fwd_v, fwd_v_quant_levels, compact_levels16
 #include "host_error.h"
 #include "launch_tally.h"
 #include "mdct_jpegenc_opt.h"

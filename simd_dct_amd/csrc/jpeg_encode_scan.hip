@@ -2,9 +2,8 @@
 // (include/mdct_jpegenc_scan.h; ITU-T T.81 A.2.3), one segment per MCU row.
 //
 // Built into its own library, libmdct_jpegenc_scan.so, linked against libmdct_hip.so (launch tally, Huffman specifications).  The
-// coefficients are the engine's own: the forward passes, the quantiser and the zig-zag compaction are compiled from mdct_kernels.hip's
-// own text (its MDCT_AAN_FWD_ONLY region, after aan_fwd.h) and the multiplier tables from own_tables.h -- the code k_px_huffman_rows
-// and mdct_fwd_u8_i16 are built from, not a restatement.
+// coefficients are the engine's own: the forward passes, the quantiser and the zig-zag compaction are aan_passes.h's and the multiplier
+// tables own_tables.h's -- the code k_px_huffman_rows and mdct_fwd_u8_i16 are built from, not a restatement.
 //
 // One kernel template, k_scan_rows<H, V> (luma sampling; chroma is 1x1): 4:2:0 <2, 2>, 4:2:2 <2, 1>, 4:4:4 <1, 1>.  One workgroup per
 // MCU row; the row is worked through in chunks of kMcus MCUs = 64 * kWaves blocks, each in a transform and a coding phase separated by
@@ -17,9 +16,7 @@
 
 #include <mutex>
 
-#include "aan_fwd.h"
-#define MDCT_AAN_FWD_ONLY
-#include "mdct_kernels.hip" // only its MDCT_AAN_FWD_ONLY region: aan_fwd_h, aan_fwd_v, fwd_v_quant_levels, compact_levels16
+#include "aan_passes.h" // aan_fwd_h, aan_fwd_v, fwd_v_quant_levels, compact_levels16
 #include "host_error.h"
 #include "launch_tally.h"
 #include "mdct_jpegenc_scan.h"

@@ -27,13 +27,12 @@
 #include "pack_rows.h"
 #include "mdct_kernels.h"
 #include "scan_records.h"
-#include "aan_fwd.h"
+#include "aan_passes.h"
 
 #pragma clang fp contract(off)
 
 namespace mdct
 {
-#ifndef MDCT_AAN_FWD_ONLY // (see the region below)
 
 // The seven butterfly constants (simd_dct.cpp:140-146) travel in the kernarg segment
 // (DctConsts, mdct_kernels.h) and therefore live in SGPRs: a VALU op with an SGPR operand is
@@ -435,9 +434,6 @@ __device__ __forceinline__ void encode_block_avx_pk(const PkConsts &K, const uin
   encode_block_avx_pk_t<SAFE, PRIO, AfterRows>(K, rows, reinterpret_cast<const f32x2 *>(qt.q), out, after_rows);
 }
 
-#ifndef MDCT_BLOCK_STAGE
-#define MDCT_BLOCK_STAGE 1
-#endif
 // Scalar tiers: the reference divides every pixel by 255 (`px / 255.f`, simd_dct.cpp:222, :343).  For a byte x the correctly rounded
 // quotient is, bit for bit,  fma(x, c, rn(x * c2))  with c = rn(1/255) and c2 = rn(1/255 - c): checked for all 256 values in exact
 // rational arithmetic (tools/check_div255_forms.py, tests/test_div255_forms.py; plain x * c is wrong for 126 of them).  Two packed
@@ -559,23 +555,12 @@ __device__ __forceinline__ uint32_t pack4_lo8(uint32_t a, uint32_t b, uint32_t c
 }
 
 constexpr int kWG = 256;           // 4 waves
-#ifndef MDCT_XCD_SWIZZLE
-#define MDCT_XCD_SWIZZLE 0
-#endif
 // Workgroup index of the launch.  Hardware hands consecutive workgroups to the 8 XCDs round-robin, so with the plain
-// linear order the 8 XCDs stream through neighbouring tiles (the same DRAM pages) at any moment; MDCT_XCD_SWIZZLE=1
-// gives every XCD one contiguous eighth of the plane instead.  Measured (profiles/r02_xcd_mapping.log): the linear order
-// is faster for every single plane (8192^2: copy 42.9 vs 51.5 us, round trip 46.8 vs 50.7, q32 31.0 vs 31.7); only the
-// 17 GB batch of config 4 gains 2 % from the swizzle.  These kernels have no reuse for an XCD's L2 to keep: linear it is.
-__device__ __forceinline__ uint32_t wg_index()
-{
-#if MDCT_XCD_SWIZZLE
-  const uint32_t w = blockIdx.x, per = gridDim.x >> 3;
-  return w < per * 8 ? (w & 7) * per + (w >> 3) : w;
-#else
-  return blockIdx.x;
-#endif
-}
+// linear order the 8 XCDs stream through neighbouring tiles (the same DRAM pages) at any moment.  A swizzle that gave
+// every XCD one contiguous eighth of the plane instead was measured (profiles/r02_xcd_mapping.log): the linear order
+// was faster for every single plane (8192^2: copy 42.9 vs 51.5 us, round trip 46.8 vs 50.7, q32 31.0 vs 31.7); only the
+// 17 GB batch of config 4 gained 2 % from the swizzle.  These kernels have no reuse for an XCD's L2 to keep: linear it is.
+__device__ __forceinline__ uint32_t wg_index() { return blockIdx.x; }
 // ---------------------------------------------------------------------------------------
 // Wave-uniform addressing.  The u8 kernels are bound by VALU issue at the clock the chip holds under their load
 // (profiles/r03_q32_timeline.md: every SIMD retires one wave per ~1.5 us, two waves in their compute phase saturate
@@ -846,10 +831,10 @@ __global__ MDCT_U8_ATTR void k_fwd_quant_u8(U8Args a)
   else if constexpr (LAYOUT == MDCT_LAYOUT_BLOCK)
   {
     // Left to itself a lane stores its block's 64 bytes as 4 x 16: every store instruction of the wave then touches a quarter of each
-    // of 64 cache lines.  MDCT_BLOCK_STAGE: the pieces go through wave-private LDS (block stride 80 B: conflict-free b128 both ways)
+    // of 64 cache lines.  In the tiled launch the pieces go through wave-private LDS (block stride 80 B: conflict-free b128 both ways)
     // and leave as four contiguous 1 KiB stores, like the q32 layout's.
     constexpr int kBlockStride = 80;
-    __shared__ __attribute__((aligned(16))) uint8_t blds[(TILED && MDCT_BLOCK_STAGE) ? (kWG / 64) * 64 * kBlockStride : 16];
+    __shared__ __attribute__((aligned(16))) uint8_t blds[TILED ? (kWG / 64) * 64 * kBlockStride : 16];
     if (valid)
     {
       uint8_t *dst = a.to + (size_t)by * a.out_strip + (size_t)bx * 64;
@@ -861,14 +846,12 @@ __global__ MDCT_U8_ATTR void k_fwd_quant_u8(U8Args a)
 #pragma unroll
         for (int j = 0; j < 4; j++)
           w[j] = pack4_lo8(q[k * 16 + j * 4], q[k * 16 + j * 4 + 1], q[k * 16 + j * 4 + 2], q[k * 16 + j * 4 + 3]);
-        if constexpr (TILED && MDCT_BLOCK_STAGE)
+        if constexpr (TILED)
           *reinterpret_cast<uint4 *>(blds + (threadIdx.x >> 6) * (64 * kBlockStride) + (threadIdx.x & 63) * kBlockStride + k * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-        else if constexpr (TILED)
-          *reinterpret_cast<u32x4_g __attribute__((address_space(1))) *>(dst_g + threadIdx.x * 64 + k * 16) = u32x4_g{w[0], w[1], w[2], w[3]};
         else
           *reinterpret_cast<uint4 *>(dst + k * 16) = make_uint4(w[0], w[1], w[2], w[3]);
       }
-      if constexpr (TILED && MDCT_BLOCK_STAGE)
+      if constexpr (TILED)
       { // the wave's 64 blocks are 4 KiB of contiguous output: read the staged pieces back so that every store instruction covers 1 KiB
         // (lane l of store k takes bytes [1024 k + 16 l, + 16) = piece l & 3 of the wave's block 16 k + (l >> 2)); wave-private, no barrier
         const uint32_t lane = threadIdx.x & 63;
@@ -1069,354 +1052,6 @@ __device__ __forceinline__ void i16_block(const DctConsts &C, const Rows rows, c
   }
 }
 
-#endif // !MDCT_AAN_FWD_ONLY
-
-// ---- MDCT_AAN_FWD_ONLY region: from here to the matching marker below is ALL that jpeg_encode_scan.hip compiles of this file
-// (it defines MDCT_AAN_FWD_ONLY and includes this file after aan_fwd.h): the AAN passes, the quantiser and the zig-zag compaction of
-// the fused pixels -> Huffman rows kernels.  The text stays here because tests/test_asm_blocks.py proves the asm blocks from this file.
-#define MDCT_LOLO "op_sel:[0,0] op_sel_hi:[0,0]"
-#define MDCT_HIHI "op_sel:[1,1] op_sel_hi:[1,1]"
-#define MDCT_LOHI "op_sel:[0,1] op_sel_hi:[0,1]" // src0.lo with src1.hi, for both halves
-#define MDCT_HILO "op_sel:[1,0] op_sel_hi:[1,0]"
-#define MDCT_SUMDIFF "op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" // (a.lo + a.hi, a.lo - a.hi) when both sources are a
-#define MDCT_XSEL " op_sel:[0,1] op_sel_hi:[1,0]"              // lo = a.lo (+) b.hi, hi = a.hi (+) b.lo (MDCT_X inside a block)
-
-// forward, one line in natural pairs (p0,p1)(p2,p3)(p4,p5)(p6,p7) -> (y0,y4) (y2,y6) (y5,y3) (y1,y7)
-__device__ __forceinline__ void aan_fwd_h_stmt(const AanPk &K, f32x2 a01, f32x2 a23, f32x2 a45, f32x2 a67, f32x2 &o04, f32x2 &o26, f32x2 &o53, f32x2 &o17)
-{
-  f32x2 t01, t23, t76, t54, e01, e32, w, o, z24, z1113;
-  MDCT_PKA(t01, a01, a67, MDCT_X);                   // (t0, t1) = (p0+p7, p1+p6)
-  MDCT_PKA(t23, a23, a45, MDCT_X);                   // (t2, t3) = (p2+p5, p3+p4)
-  MDCT_PKA(t76, a01, a67, MDCT_X " " MDCT_NEG_B);    // (t7, t6) = (p0-p7, p1-p6)
-  MDCT_PKA(t54, a23, a45, MDCT_X " " MDCT_NEG_B);    // (t5, t4) = (p2-p5, p3-p4)
-  MDCT_PKA(e01, t01, t23, MDCT_X);                   // (e10, e11) = (t0+t3, t1+t2)
-  MDCT_PKA(e32, t01, t23, MDCT_X " " MDCT_NEG_B);    // (e13, e12) = (t0-t3, t1-t2)
-  MDCT_PKA(o04, e01, e01, MDCT_SUMDIFF);                  // (e10+e11, e10-e11)
-  w.x = e32.y + e32.x;                               // s1 = e12 + e13
-  w.y = t54.x + t76.y;                               // o11 = t5 + t6
-  o.x = t54.y + t54.x;                               // o10 = t4 + t5
-  o.y = t76.y + t76.x;                               // o12 = t6 + t7
-  f32x2 z5;
-  z5.x = (o.x - o.y) * K.c707_382.y;                 // z5 = (o10 - o12) * c382
-  z5.y = z5.x;
-  MDCT_PKF(z24, o, K.c541_1306, z5, "op_sel:[0,0,0] op_sel_hi:[1,1,0]");                   // (z2, z4) = (c541 o10 + z5, c1306 o12 + z5)
-  MDCT_PKF(z1113, w, K.c707_382, t76, "op_sel:[1,0,0] op_sel_hi:[1,0,0] neg_hi:[1,0,0]");  // (z11, z13) = (o11 c707 + t7, -o11 c707 + t7)
-  MDCT_PKF(o26, w, K.c707_382, e32, "op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_hi:[1,0,0]");    // (s1 c707 + e13, -s1 c707 + e13)
-  MDCT_PKA(o53, z1113, z24, MDCT_HILO " neg_hi:[0,1]"); // (z13+z2, z13-z2)
-  MDCT_PKA(o17, z1113, z24, MDCT_LOHI " neg_hi:[0,1]"); // (z11+z4, z11-z4)
-}
-
-// forward down a pair of columns, in place (direct image of aan_fwd8)
-__device__ __forceinline__ void aan_fwd_v_stmt(const AanPk &K, f32x2 (&p)[8])
-{
-  f32x2 t0, t7, t1, t6, t2, t5, t3, t4, e10, e13, e11, e12, s1, o10, o11, o12, z5, z2, z4, z11, z13;
-  MDCT_PKA(t0, p[0], p[7], ""); MDCT_PKA(t7, p[0], p[7], MDCT_NEG_B); MDCT_PKA(t1, p[1], p[6], ""); MDCT_PKA(t6, p[1], p[6], MDCT_NEG_B);
-  MDCT_PKA(t2, p[2], p[5], ""); MDCT_PKA(t5, p[2], p[5], MDCT_NEG_B); MDCT_PKA(t3, p[3], p[4], ""); MDCT_PKA(t4, p[3], p[4], MDCT_NEG_B);
-  MDCT_PKA(e10, t0, t3, ""); MDCT_PKA(e13, t0, t3, MDCT_NEG_B); MDCT_PKA(e11, t1, t2, ""); MDCT_PKA(e12, t1, t2, MDCT_NEG_B);
-  MDCT_PKA(s1, e12, e13, "");
-  MDCT_PKA(o10, t4, t5, ""); MDCT_PKA(o11, t5, t6, ""); MDCT_PKA(o12, t6, t7, "");
-  MDCT_PKA(z5, o10, o12, MDCT_NEG_B); MDCT_PKM(z5, z5, K.c707_382, MDCT_K_HH);
-  MDCT_PKF(z2, o10, K.c541_1306, z5, "op_sel:[0,0,0] op_sel_hi:[1,0,1]");
-  MDCT_PKF(z4, o12, K.c541_1306, z5, "op_sel:[0,1,0] op_sel_hi:[1,1,1]");
-  MDCT_PKF(z11, o11, K.c707_382, t7, "op_sel:[0,0,0] op_sel_hi:[1,0,1]");
-  MDCT_PKF(z13, o11, K.c707_382, t7, "op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]");
-  MDCT_PKA(p[0], e10, e11, ""); MDCT_PKA(p[4], e10, e11, MDCT_NEG_B);
-  MDCT_PKF(p[2], s1, K.c707_382, e13, "op_sel:[0,0,0] op_sel_hi:[1,0,1]");
-  MDCT_PKF(p[6], s1, K.c707_382, e13, "op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]");
-  MDCT_PKA(p[5], z13, z2, ""); MDCT_PKA(p[3], z13, z2, MDCT_NEG_B);
-  MDCT_PKA(p[1], z11, z4, ""); MDCT_PKA(p[7], z11, z4, MDCT_NEG_B);
-}
-
-// inverse down a pair of columns, in place (direct image of aan_inv8)
-__device__ __forceinline__ void aan_inv_v_stmt(const AanPk &K, f32x2 (&p)[8])
-{
-  f32x2 e10, e11, e13, e12, t0, t3, t1, t2, z13, z10, z11, z12, t7, d, z5, o10, o12, t6, t5, t4;
-  MDCT_PKA(e10, p[0], p[4], ""); MDCT_PKA(e11, p[0], p[4], MDCT_NEG_B);
-  MDCT_PKA(e13, p[2], p[6], "");
-  MDCT_PKA(d, p[2], p[6], MDCT_NEG_B); MDCT_PKF(e12, d, K.c1414_1847, e13, "op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]");
-  MDCT_PKA(t0, e10, e13, ""); MDCT_PKA(t3, e10, e13, MDCT_NEG_B); MDCT_PKA(t1, e11, e12, ""); MDCT_PKA(t2, e11, e12, MDCT_NEG_B);
-  MDCT_PKA(z13, p[5], p[3], ""); MDCT_PKA(z10, p[5], p[3], MDCT_NEG_B); MDCT_PKA(z11, p[1], p[7], ""); MDCT_PKA(z12, p[1], p[7], MDCT_NEG_B);
-  MDCT_PKA(t7, z11, z13, "");
-  MDCT_PKA(d, z11, z13, MDCT_NEG_B);
-  MDCT_PKA(z5, z10, z12, ""); MDCT_PKM(z5, z5, K.c1414_1847, MDCT_K_HH);
-  MDCT_PKF(o10, z12, K.c1082_2613, z5, "op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]");
-  MDCT_PKF(o12, z10, K.c1082_2613, z5, "op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]");
-  MDCT_PKA(t6, o12, t7, MDCT_NEG_B);
-  MDCT_PKF(t5, d, K.c1414_1847, t6, "op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]");
-  MDCT_PKA(t4, o10, t5, "");
-  MDCT_PKA(p[0], t0, t7, ""); MDCT_PKA(p[7], t0, t7, MDCT_NEG_B);
-  MDCT_PKA(p[1], t1, t6, ""); MDCT_PKA(p[6], t1, t6, MDCT_NEG_B);
-  MDCT_PKA(p[2], t2, t5, ""); MDCT_PKA(p[5], t2, t5, MDCT_NEG_B);
-  MDCT_PKA(p[4], t3, t4, ""); MDCT_PKA(p[3], t3, t4, MDCT_NEG_B);
-}
-
-// inverse, one line given as (c0,c4) (c2,c6) (c5,c3) (c1,c7) -> (x0,x7) (x1,x6) (x2,x5) (x4,x3)
-__device__ __forceinline__ void aan_inv_h_stmt(const AanPk &K, f32x2 i04, f32x2 i26, f32x2 i53, f32x2 i17, f32x2 &o07, f32x2 &o16, f32x2 &o25, f32x2 &o43)
-{
-  f32x2 e, f, t03, t12, z3, z1, td, u, v;
-  MDCT_PKA(e, i04, i04, MDCT_SUMDIFF);                    // (e10, e11) = (c0+c4, c0-c4)
-  MDCT_PKA(f, i26, i26, MDCT_SUMDIFF);                    // (e13, c2-c6)
-  f.y = __builtin_fmaf(f.y, K.c1414_1847.x, -f.x);   // e12 = (c2-c6)*sqrt2 - e13, fused
-  MDCT_PKA(t03, e, f, MDCT_LOLO " neg_hi:[0,1]");       // (t0, t3) = (e10+e13, e10-e13)
-  MDCT_PKA(t12, e, f, MDCT_HIHI " neg_hi:[0,1]");       // (t1, t2) = (e11+e12, e11-e12)
-  MDCT_PKA(z3, i53, i53, MDCT_SUMDIFF);                   // (z13, z10) = (c5+c3, c5-c3)
-  MDCT_PKA(z1, i17, i17, MDCT_SUMDIFF);                   // (z11, z12) = (c1+c7, c1-c7)
-  MDCT_PKA(td, z1, z3, MDCT_LOLO " neg_hi:[0,1]");      // (t7, z11-z13)
-  const float z5 = (z3.y + z1.y) * K.c1414_1847.y;   // (z10 + z12) * c1847
-  const float o10 = __builtin_fmaf(K.c1082_2613.x, z1.y, -z5);
-  const float o12 = __builtin_fmaf(-K.c1082_2613.y, z3.y, z5);
-  u.x = o12 - td.x;                                  // t6
-  u.y = __builtin_fmaf(td.y, K.c1414_1847.x, -u.x);  // t5 = (z11-z13)*sqrt2 - t6, fused
-  v.x = o10 + u.y;                                   // t4
-  MDCT_PKA(o07, t03, td, MDCT_LOLO " neg_hi:[0,1]");    // (t0+t7, t0-t7)
-  MDCT_PKA(o16, t12, u, MDCT_LOLO " neg_hi:[0,1]");     // (t1+t6, t1-t6)
-  MDCT_PKA(o25, t12, u, MDCT_HIHI " neg_hi:[0,1]");     // (t2+t5, t2-t5)
-  MDCT_PKA(o43, t03, v, MDCT_HILO " neg_hi:[0,1]");     // (t3+t4, t3-t4)
-}
-
-
-// ---------------------------------------------------------------------------------------
-// The same four passes as ASM BLOCKS (round 5).  One asm statement per operation costs wait states the hardware does not need: for an asm
-// statement that reads a VGPR written by the asm statement right before it the compiler inserts an s_nop (it cannot see inside and assumes
-// the gfx940 dst_sel forwarding hazard, which a v_pk_*_f32 does not have) -- 97 of them per wave in k_u8_batch, 60-70 in the int16 round
-// trip, each an issue slot.  The column passes are pure packed sequences: one block of 34 instructions each, registers allocated by hand,
-// results left in a PERMUTATION of the input registers (renaming is free for the caller).  The row passes keep their 6 / 12 unpaired scalar
-// operations as compiler-visible code (an inline-asm operand cannot name half of a register pair) between two blocks of packed operations.
-// Same operations, same operands, same order of operands in every subtraction as the _stmt forms above (MDCT_AAN_BLOCKS=0 builds those).
-// ---------------------------------------------------------------------------------------
-#ifndef MDCT_AAN_BLOCKS
-#define MDCT_AAN_BLOCKS 1
-#endif
-#define MDCT_SUB " neg_lo:[0,1] neg_hi:[0,1]\n\t"
-#define MDCT_KLO " op_sel:[0,0] op_sel_hi:[1,0]\n\t" // times the constant pair's low half, both halves
-#define MDCT_KHI " op_sel:[0,1] op_sel_hi:[1,1]\n\t" // times its high half
-// v_pk_fma_f32 d, a, k, c: a * (the constant pair's low / high half, both halves) + c; _NA negates a (-a k + c), _NC negates c (a k - c)
-#define MDCT_FKLO " op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
-#define MDCT_FKHI " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-#define MDCT_FKLO_NA " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"
-#define MDCT_FKHI_NA " op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"
-#define MDCT_FKLO_NC " op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]\n\t"
-
-__device__ __forceinline__ void aan_fwd_v(const AanPk &K, f32x2 (&p)[8])
-{
-#if !MDCT_AAN_BLOCKS
-  aan_fwd_v_stmt(K, p);
-#else
-  f32x2 r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3], r4 = p[4], r5 = p[5], r6 = p[6], r7 = p[7], T;
-  asm("v_pk_add_f32 %8, %0, %7\n\t"            /* T  = t0 = p0 + p7 */
-      "v_pk_add_f32 %7, %0, %7" MDCT_SUB       /* r7 = t7 = p0 - p7 */
-      "v_pk_add_f32 %0, %1, %6\n\t"            /* r0 = t1 */
-      "v_pk_add_f32 %6, %1, %6" MDCT_SUB       /* r6 = t6 */
-      "v_pk_add_f32 %1, %2, %5\n\t"            /* r1 = t2 */
-      "v_pk_add_f32 %5, %2, %5" MDCT_SUB       /* r5 = t5 */
-      "v_pk_add_f32 %2, %3, %4\n\t"            /* r2 = t3 */
-      "v_pk_add_f32 %4, %3, %4" MDCT_SUB       /* r4 = t4 */
-      "v_pk_add_f32 %3, %8, %2\n\t"            /* r3 = e10 = t0 + t3 */
-      "v_pk_add_f32 %2, %8, %2" MDCT_SUB       /* r2 = e13 = t0 - t3 */
-      "v_pk_add_f32 %8, %0, %1\n\t"            /* T  = e11 = t1 + t2 */
-      "v_pk_add_f32 %1, %0, %1" MDCT_SUB       /* r1 = e12 = t1 - t2 */
-      "v_pk_add_f32 %0, %3, %8\n\t"            /* r0 = out0 = e10 + e11 */
-      "v_pk_add_f32 %8, %3, %8" MDCT_SUB       /* T  = out4 = e10 - e11 */
-      "v_pk_add_f32 %3, %1, %2\n\t"            /* r3 = s1 = e12 + e13 */
-      "v_pk_add_f32 %1, %4, %5\n\t"            /* r1 = o10 = t4 + t5            (e12 is dead) */
-      "v_pk_add_f32 %4, %5, %6\n\t"            /* r4 = o11 = t5 + t6 */
-      "v_pk_add_f32 %5, %6, %7\n\t"            /* r5 = o12 = t6 + t7 */
-      "v_pk_fma_f32 %6, %3, %9, %2" MDCT_FKLO_NA /* r6 = out6 = -s1 c707 + e13 */
-      "v_pk_fma_f32 %2, %3, %9, %2" MDCT_FKLO    /* r2 = out2 = s1 c707 + e13 */
-      "v_pk_add_f32 %3, %1, %5" MDCT_SUB       /* r3 = o10 - o12 */
-      "v_pk_mul_f32 %3, %3, %9" MDCT_KHI       /* r3 = z5 = (o10 - o12) c382 */
-      "v_pk_fma_f32 %1, %1, %10, %3" MDCT_FKLO   /* r1 = z2 = o10 c541 + z5 */
-      "v_pk_fma_f32 %5, %5, %10, %3" MDCT_FKHI   /* r5 = z4 = o12 c1306 + z5 */
-      "v_pk_fma_f32 %3, %4, %9, %7" MDCT_FKLO    /* r3 = z11 = o11 c707 + t7 */
-      "v_pk_fma_f32 %7, %4, %9, %7" MDCT_FKLO_NA /* r7 = z13 = -o11 c707 + t7 */
-      "v_pk_add_f32 %4, %7, %1\n\t"            /* r4 = out5 = z13 + z2 */
-      "v_pk_add_f32 %7, %7, %1" MDCT_SUB       /* r7 = out3 = z13 - z2 */
-      "v_pk_add_f32 %1, %3, %5\n\t"            /* r1 = out1 = z11 + z4 */
-      "v_pk_add_f32 %3, %3, %5 neg_lo:[0,1] neg_hi:[0,1]" /* r3 = out7 = z11 - z4 */
-      : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "=&v"(T)
-      : "s"(K.c707_382), "s"(K.c541_1306));
-  p[0] = r0; p[1] = r1; p[2] = r2; p[3] = r7; p[4] = T; p[5] = r4; p[6] = r6; p[7] = r3;
-#endif
-}
-
-__device__ __forceinline__ void aan_inv_v(const AanPk &K, f32x2 (&p)[8])
-{
-#if !MDCT_AAN_BLOCKS
-  aan_inv_v_stmt(K, p);
-#else
-  f32x2 r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3], r4 = p[4], r5 = p[5], r6 = p[6], r7 = p[7], T;
-  asm("v_pk_add_f32 %8, %0, %4\n\t"            /* T  = e10 = p0 + p4 */
-      "v_pk_add_f32 %4, %0, %4" MDCT_SUB       /* r4 = e11 = p0 - p4 */
-      "v_pk_add_f32 %0, %2, %6\n\t"            /* r0 = e13 = p2 + p6 */
-      "v_pk_add_f32 %6, %2, %6" MDCT_SUB       /* r6 = p2 - p6 */
-      "v_pk_add_f32 %2, %5, %3\n\t"            /* r2 = z13 = p5 + p3 */
-      "v_pk_add_f32 %3, %5, %3" MDCT_SUB       /* r3 = z10 = p5 - p3 */
-      "v_pk_add_f32 %5, %1, %7\n\t"            /* r5 = z11 = p1 + p7 */
-      "v_pk_add_f32 %7, %1, %7" MDCT_SUB       /* r7 = z12 = p1 - p7 */
-      "v_pk_fma_f32 %6, %6, %9, %0" MDCT_FKLO_NC /* r6 = e12 = (p2 - p6) c1414 - e13 */
-      "v_pk_add_f32 %1, %5, %2\n\t"            /* r1 = t7 = z11 + z13 */
-      "v_pk_add_f32 %5, %5, %2" MDCT_SUB       /* r5 = z11 - z13 */
-      "v_pk_add_f32 %2, %3, %7\n\t"            /* r2 = z10 + z12 */
-      "v_pk_mul_f32 %2, %2, %9" MDCT_KHI       /* r2 = z5 = (z10 + z12) c1847 */
-      "v_pk_fma_f32 %7, %7, %10, %2" MDCT_FKLO_NC /* r7 = o10 = z12 c1082 - z5 */
-      "v_pk_fma_f32 %3, %3, %10, %2" MDCT_FKHI_NA /* r3 = o12 = -z10 c2613 + z5 */
-      "v_pk_add_f32 %2, %8, %0\n\t"            /* r2 = t0 = e10 + e13 */
-      "v_pk_add_f32 %0, %8, %0" MDCT_SUB       /* r0 = t3 = e10 - e13 */
-      "v_pk_add_f32 %3, %3, %1" MDCT_SUB       /* r3 = t6 = o12 - t7 */
-      "v_pk_add_f32 %8, %4, %6\n\t"            /* T  = t1 = e11 + e12 */
-      "v_pk_add_f32 %6, %4, %6" MDCT_SUB       /* r6 = t2 = e11 - e12 */
-      "v_pk_fma_f32 %5, %5, %9, %3" MDCT_FKLO_NC /* r5 = t5 = (z11 - z13) c1414 - t6 */
-      "v_pk_add_f32 %4, %2, %1\n\t"            /* r4 = out0 = t0 + t7 */
-      "v_pk_add_f32 %2, %2, %1" MDCT_SUB       /* r2 = out7 = t0 - t7 */
-      "v_pk_add_f32 %7, %7, %5\n\t"            /* r7 = t4 = o10 + t5 */
-      "v_pk_add_f32 %1, %8, %3\n\t"            /* r1 = out1 = t1 + t6 */
-      "v_pk_add_f32 %8, %8, %3" MDCT_SUB       /* T  = out6 = t1 - t6 */
-      "v_pk_add_f32 %3, %6, %5\n\t"            /* r3 = out2 = t2 + t5 */
-      "v_pk_add_f32 %6, %6, %5" MDCT_SUB       /* r6 = out5 = t2 - t5 */
-      "v_pk_add_f32 %5, %0, %7\n\t"            /* r5 = out4 = t3 + t4 */
-      "v_pk_add_f32 %0, %0, %7 neg_lo:[0,1] neg_hi:[0,1]" /* r0 = out3 = t3 - t4 */
-      : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "=&v"(T)
-      : "s"(K.c1414_1847), "s"(K.c1082_2613));
-  p[0] = r4; p[1] = r1; p[2] = r3; p[3] = r0; p[4] = r5; p[5] = r6; p[6] = T; p[7] = r2;
-#endif
-}
-
-// forward, one line in natural pairs (p0,p1)(p2,p3)(p4,p5)(p6,p7) -> (y0,y4) (y2,y6) (y5,y3) (y1,y7)
-__device__ __forceinline__ void aan_fwd_h(const AanPk &K, f32x2 a01, f32x2 a23, f32x2 a45, f32x2 a67, f32x2 &o04, f32x2 &o26, f32x2 &o53, f32x2 &o17)
-{
-#if !MDCT_AAN_BLOCKS
-  aan_fwd_h_stmt(K, a01, a23, a45, a67, o04, o26, o53, o17);
-#else
-  f32x2 T0, T1;
-  asm("v_pk_add_f32 %4, %0, %3" MDCT_XSEL "\n\t"                               /* T0 = (t0, t1) = (p0+p7, p1+p6) */
-      "v_pk_add_f32 %5, %1, %2" MDCT_XSEL "\n\t"                               /* T1 = (t2, t3) = (p2+p5, p3+p4) */
-      "v_pk_add_f32 %0, %0, %3" MDCT_XSEL " neg_lo:[0,1] neg_hi:[0,1]\n\t"     /* A  = (t7, t6) = (p0-p7, p1-p6) */
-      "v_pk_add_f32 %1, %1, %2" MDCT_XSEL " neg_lo:[0,1] neg_hi:[0,1]\n\t"     /* B  = (t5, t4) = (p2-p5, p3-p4) */
-      "v_pk_add_f32 %2, %4, %5" MDCT_XSEL "\n\t"                               /* C  = (e10, e11) = (t0+t3, t1+t2) */
-      "v_pk_add_f32 %3, %4, %5" MDCT_XSEL " neg_lo:[0,1] neg_hi:[0,1]\n\t"     /* D  = (e13, e12) = (t0-t3, t1-t2) */
-      "v_pk_add_f32 %4, %2, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]"      /* T0 = (e10+e11, e10-e11) */
-      : "+v"(a01), "+v"(a23), "+v"(a45), "+v"(a67), "=&v"(T0), "=&v"(T1));
-  const f32x2 t76 = a01, t54 = a23, e32 = a67;
-  o04 = T0;
-  f32x2 w, o, z5;
-  w.x = e32.y + e32.x;                               // s1 = e12 + e13
-  w.y = t54.x + t76.y;                               // o11 = t5 + t6
-  o.x = t54.y + t54.x;                               // o10 = t4 + t5
-  o.y = t76.y + t76.x;                               // o12 = t6 + t7
-  z5.x = (o.x - o.y) * K.c707_382.y;                 // z5 = (o10 - o12) * c382
-  z5.y = z5.x;
-  f32x2 T;
-  asm("v_pk_fma_f32 %1, %1, %9, %7 op_sel:[0,0,0] op_sel_hi:[1,1,0]\n\t"                  /* o  = (z2, z4) = (o10 c541 + z5, o12 c1306 + z5) */
-      "v_pk_fma_f32 %2, %0, %8, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0] neg_hi:[1,0,0]\n\t"   /* T  = (z11, z13) = (o11 c707 + t7, -o11 c707 + t7) */
-      "v_pk_fma_f32 %3, %0, %8, %6 op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_hi:[1,0,0]\n\t"   /* o26 = (s1 c707 + e13, -s1 c707 + e13) */
-      "v_pk_add_f32 %4, %2, %1 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]\n\t"             /* o53 = (z13+z2, z13-z2) */
-      "v_pk_add_f32 %2, %2, %1 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]"                 /* T -> o17 = (z11+z4, z11-z4) */
-      : "+v"(w), "+v"(o), "=&v"(T), "=&v"(o26), "=&v"(o53)
-      : "v"(t76), "v"(e32), "v"(z5), "s"(K.c707_382), "s"(K.c541_1306));
-  o17 = T;
-#endif
-}
-
-// inverse, one line given as (c0,c4) (c2,c6) (c5,c3) (c1,c7) -> (x0,x7) (x1,x6) (x2,x5) (x4,x3)
-__device__ __forceinline__ void aan_inv_h(const AanPk &K, f32x2 i04, f32x2 i26, f32x2 i53, f32x2 i17, f32x2 &o07, f32x2 &o16, f32x2 &o25, f32x2 &o43)
-{
-#if !MDCT_AAN_BLOCKS
-  aan_inv_h_stmt(K, i04, i26, i53, i17, o07, o16, o25, o43);
-#else
-  f32x2 td;
-  asm("v_pk_add_f32 %0, %0, %0 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]\n\t"  /* e  = (e10, e11) = (c0+c4, c0-c4) */
-      "v_pk_add_f32 %1, %1, %1 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]\n\t"  /* f  = (e13, c2-c6) */
-      "v_pk_add_f32 %2, %2, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]\n\t"  /* z3 = (z13, z10) = (c5+c3, c5-c3) */
-      "v_pk_add_f32 %3, %3, %3 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]\n\t"  /* z1 = (z11, z12) = (c1+c7, c1-c7) */
-      "v_pk_add_f32 %4, %3, %2 op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]"      /* td = (t7, z11-z13) */
-      : "+v"(i04), "+v"(i26), "+v"(i53), "+v"(i17), "=&v"(td));
-  f32x2 f = i26, u;
-  f.y = __builtin_fmaf(f.y, K.c1414_1847.x, -f.x);       // e12 = (c2-c6)*sqrt2 - e13, fused
-  const float z5 = (i53.y + i17.y) * K.c1414_1847.y;     // (z10 + z12) * c1847
-  const float o10 = __builtin_fmaf(K.c1082_2613.x, i17.y, -z5);
-  const float o12 = __builtin_fmaf(-K.c1082_2613.y, i53.y, z5);
-  u.x = o12 - td.x;                                      // t6
-  u.y = __builtin_fmaf(td.y, K.c1414_1847.x, -u.x);      // t5 = (z11-z13)*sqrt2 - t6, fused
-  td.y = o10 + u.y;                                      // t4 (z11-z13 is dead: its half of td carries t4 into the block below)
-  f32x2 t03, t12;
-  asm("v_pk_add_f32 %4, %6, %7 op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]\n\t"  /* t03 = (t0, t3) = (e10+e13, e10-e13) */
-      "v_pk_add_f32 %5, %6, %7 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]\n\t"  /* t12 = (t1, t2) = (e11+e12, e11-e12) */
-      "v_pk_add_f32 %0, %4, %8 op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]\n\t"  /* o07 = (t0+t7, t0-t7) */
-      "v_pk_add_f32 %3, %4, %8 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]\n\t"  /* o43 = (t3+t4, t3-t4) */
-      "v_pk_add_f32 %1, %5, %9 op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]\n\t"  /* o16 = (t1+t6, t1-t6) */
-      "v_pk_add_f32 %2, %5, %9 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]"      /* o25 = (t2+t5, t2-t5) */
-      : "=&v"(o07), "=&v"(o16), "=&v"(o25), "=&v"(o43), "=&v"(t03), "=&v"(t12)
-      : "v"(i04), "v"(f), "v"(td), "v"(u));
-#endif
-}
-
-// ---------------------------------------------------------------------------------------
-// The back half of the fused pixels -> Huffman rows kernels, after the row passes left the block in P (aan_fwd_h).
-// ---------------------------------------------------------------------------------------
-// Column passes and quantiser: quantised levels as the low 16 bits of val[] (natural order v*8+u): the DC like the int16 plane would
-// hold it (sat_i16), the AC coefficients saturated to the +-1023 of baseline categories 1..10 -- exactly what the staged coder does to
-// an int16 record at token time.  qf: the 32 multiplier pairs in the pair order of the column pass (make_own_tables, pair_order), in
-// the kernel's argument segment; dc_shift: 64 * 128 with the level shift (exactly "raw DC minus 64 * 128"), else 0.
-// CLAMP = false: the caller knows that no level can leave those ranges, and the 64 saturations per block are left out.
-template <bool CLAMP>
-__device__ __forceinline__ void fwd_v_quant_levels(const AanPk &K, f32x2 (&P)[4][8], karg_pairs_t qf, float dc_shift, uint32_t (&val)[64])
-{
-  constexpr int kA[4] = {0, 2, 5, 1}, kB[4] = {4, 6, 3, 7};
-  const f32x2 magic_v = K.magic;
-#pragma unroll
-  for (int j = 0; j < 4; j++)
-  {
-    aan_fwd_v(K, P[j]);
-    if (j == 0)
-      P[0][0].x = P[0][0].x - dc_shift;
-    // the 8 multiplier pairs of column pair j, fetched here (all 64 multipliers held in SGPRs from the top of the kernel spilled)
-    karg_pairs_t tq = qf + j * 8;
-    asm volatile("" : "+s"(tq));
-#pragma unroll
-    for (int v = 0; v < 8; v++)
-    {
-      f32x2 c;
-      MDCT_PKF(c, P[j][v], tq[v], magic_v, "op_sel:[0,0,0] op_sel_hi:[1,1,0]"); // quant_i16_bits; the clamps (baseline JPEG: AC to +-1023) on the biased value
-      const bool is_dc = j == 0 && v == 0;
-      if constexpr (CLAMP)
-        c = f32x2{__builtin_amdgcn_fmed3f(c.x, is_dc ? kQLo : kMagic23 - 1023.0f, is_dc ? kQHi : kMagic23 + 1023.0f), __builtin_amdgcn_fmed3f(c.y, kMagic23 - 1023.0f, kMagic23 + 1023.0f)};
-      val[v * 8 + kA[j]] = __float_as_uint(c.x);
-      val[v * 8 + kB[j]] = __float_as_uint(c.y);
-    }
-  }
-}
-
-// Zig-zag order; AC entries run << 12 | level compacted to the front of the lane's LDS row rec (kRec16Row halfwords), a ZRL entry for
-// every 16 zeros in a row.  EVERY coefficient writes run << 12 | level at the current position and only those that need an entry
-// advance it: a zero's write is overwritten by the next entry -- unless it is the 16th zero in a row, and then what it
-// wrote, 15 << 12 | 0, IS the ZRL entry.  (7 vector instructions per coefficient; selecting value and address per
-// coefficient and tracking the last non-zero took 11.)  Returns the number of entries; ZRL entries after the last coefficient are
-// dropped (at most three: 62 zeros).  my_dc: the DC level; need_eob: position 63 is not coded.
-__device__ __forceinline__ uint32_t compact_levels16(const uint32_t (&val)[64], uint16_t *rec, int &my_dc, bool &need_eob)
-{
-  uint32_t pos = 0, r12 = 0;
-#pragma unroll
-  for (int k = 1; k < 64; k++)
-  {
-    const uint32_t v = val[kZigZag[k]];
-    const bool nz = (v & 0xFFFFu) != 0;
-    const bool wr = nz || r12 == 0xF000u;
-    rec[pos] = (uint16_t)((v & 0xFFFu) | r12);
-    pos += wr ? 1u : 0u;
-    r12 = wr ? 0u : r12 + 0x1000u;
-  }
-  uint32_t n = pos;
-#pragma unroll
-  for (int t = 0; t < 3; t++)
-    n -= (n > 0 && rec[n - 1] == 0xF000u) ? 1u : 0u;
-  my_dc = (int)(int16_t)(val[0] & 0xFFFFu);
-  need_eob = (val[kZigZag[63]] & 0xFFFFu) == 0;
-  return n;
-}
-
-// ---- end of the MDCT_AAN_FWD_ONLY region
-#ifndef MDCT_AAN_FWD_ONLY
-
 // quantise -> dequantise of the eight pairs of one column pair, SAT-free: c = rne(y qf) by the fused magic add (quant_i16_bits) and the subtract, z = c dq
 __device__ __forceinline__ void quant_dequant8(const AanPk &K, f32x2 (&p)[8], const f32x2 (&qf)[8], const f32x2 (&dq)[8])
 {
@@ -1476,7 +1111,7 @@ __device__ __forceinline__ kbytes_t const_bytes(const void *p)
 template <bool SAT>
 __device__ __forceinline__ void quant_dequant_pairs(const AanPk &K, f32x2 (&p)[8], karg_pairs_t tq, karg_pairs_t td)
 {
-  if constexpr (!SAT && MDCT_AAN_BLOCKS)
+  if constexpr (!SAT)
   {
     const f32x2 qf[8] = {tq[0], tq[1], tq[2], tq[3], tq[4], tq[5], tq[6], tq[7]}, dq[8] = {td[0], td[1], td[2], td[3], td[4], td[5], td[6], td[7]};
     quant_dequant8(K, p, qf, dq);
@@ -1851,9 +1486,6 @@ __device__ __forceinline__ void u8_rows(const DctConsts &C, const f32x2 shifts, 
 #ifndef MDCT_U8B_WAVES_SMALL
 #define MDCT_U8B_WAVES_SMALL 4
 #endif
-#ifndef MDCT_U8B_PRIO
-#define MDCT_U8B_PRIO true
-#endif
 // GENERAL = false: every plane's table is tame (mdct_api.hip: u8_table_is_tame / u8_table_is_bounded): no saturations in the quantiser.
 // (The output stage saturates by itself in every build.)  U8_INV is always GENERAL: its coefficients are the caller's, not a transform's.
 template <int MODE, bool GENERAL, bool SMALL>
@@ -1873,8 +1505,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SMALL ? MDCT
   char *dst = (char *)t.to() + ((size_t)t.row * 8 * pout + (size_t)t.b0 * 8) * out_el;
   const uint32_t hop = (t.straddle && lane >= t.s) ? 0xFFFFFFFFu : 0u;
   const uint32_t hop_in = ((uint32_t)pin - t.bpr()) * (8 * in_el), hop_out = ((uint32_t)pout - t.bpr()) * (8 * out_el);
-  u8_rows<MODE, GENERAL, MDCT_U8B_PRIO>(a.consts, shifts, src, dst, pin, pout, lane * (8 * in_el) + (hop & hop_in),
-                                                                                           lane * (8 * out_el) + (hop & hop_out), t.tables);
+  u8_rows<MODE, GENERAL, true>(a.consts, shifts, src, dst, pin, pout, lane * (8 * in_el) + (hop & hop_in), lane * (8 * out_el) + (hop & hop_out), t.tables);
 }
 
 // The reference's primary product (B1, simd_dct.cpp:2064-2262: k_q32_tile above) on a plane batch: any list of separately allocated 8-bit planes,
@@ -2163,7 +1794,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_px_huffman_rows(PxHuffArgs a)
       }
       aan_fwd_h(K, a01, a23, a45, a67, P[0][r], P[1][r], P[2][r], P[3][r]);
     }
-    // ---- column passes, quantiser, zig-zag compaction into the lane's LDS row (the MDCT_AAN_FWD_ONLY region above)
+    // ---- column passes, quantiser, zig-zag compaction into the lane's LDS row (aan_passes.h)
     uint32_t val[64];
     fwd_v_quant_levels<CLAMP>(K, P, karg_pairs(offsetof(PxHuffArgs, tb) + offsetof(OwnTables, qf)), a.dc_shift, val);
     int my_dc;
@@ -2535,15 +2166,12 @@ hipError_t launch_fwd_quant_u8(const U8Args &a, int layout, int profile, bool sa
   return hipErrorInvalidValue;
 }
 
-#ifndef MDCT_I16_TILED
-#define MDCT_I16_TILED 1
-#endif
 template <int MODE>
 static hipError_t launch_i16_m(const I16Args &a, bool has_lut, bool lut_bounded, hipStream_t s)
 {
   const uint32_t launch_rows = a.nblocks / a.bpr;
   constexpr bool RT = MODE == MODE_ROUNDTRIP; // the only mode with a build without saturations
-  if (MDCT_I16_TILED && a.bpr % 64 == 0 && launch_rows <= 65535u)
+  if (a.bpr % 64 == 0 && launch_rows <= 65535u)
   {
     const dim3 g(a.bpr / 64, launch_rows);
     const uint64_t tiles = (uint64_t)g.x * g.y;
@@ -2768,5 +2396,4 @@ hipError_t launch_stream_copy(const void *from, void *to, size_t bytes, int cus,
   return hipGetLastError();
 }
 
-#endif // !MDCT_AAN_FWD_ONLY
 } // namespace mdct

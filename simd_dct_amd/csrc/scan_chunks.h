@@ -12,9 +12,9 @@
 // ChunkGrid holds what does not depend on where the levels come from: which block a lane takes and the read-out of a block.  The
 // source is a class on top of it: ScanChunks here (pixels -> AAN -> quantiser), CoefChunks (coef_chunks.h: a fetch from a
 // coefficient plane).  The symbols phase and the epilogue are the kernels' (k_scan_rows its own, k_opt and k_coef: opt_symbols.h).
-// Include after aan_fwd.h and mdct_kernels.hip's MDCT_AAN_FWD_ONLY region.  Device code only.
+// Device code only.
 #pragma once
-#include "aan_fwd.h"
+#include "aan_passes.h"
 #include "huffman_rows.h"
 #include "own_tables.h"
 #include "scan_order.h"

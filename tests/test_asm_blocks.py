@@ -1,14 +1,18 @@
-"""Symbolic execution of the hand-written packed-fp32 asm blocks of the engine-own transforms (csrc/mdct_kernels.hip: aan_fwd_v,
-aan_inv_v, aan_fwd_h, aan_inv_h, quant_dequant8) against the scalar definition they must reproduce operation for operation
+"""Symbolic execution of the hand-written packed-fp32 asm blocks of the engine-own transforms (csrc/aan_passes.h: aan_fwd_v, aan_inv_v,
+aan_fwd_h, aan_inv_h; csrc/mdct_kernels.hip: quant_dequant8) against the scalar definition they must reproduce operation for operation
 (aan_fwd8 / aan_inv8 -- the arithmetic oracle/dct_oracle.c restates): every block is parsed out of the source, run on symbols with the
 v_pk_* operand-select / negate semantics, and the expression TREE of every result -- which operands meet in which operation, in which
 order for the subtractions -- must equal the tree of the definition (addition and multiplication are commutative bit for bit in IEEE
-arithmetic, nothing else is assumed).  The GPU parity tests then only have to confirm what is already proven here."""
+arithmetic, nothing else is assumed).  The GPU parity tests then only have to confirm what is already proven here.  The text proven
+is the only text: each of the five functions is defined once in csrc/, and no file there includes a .hip file."""
+import glob
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = open(os.path.join(ROOT, "simd_dct_amd", "csrc", "mdct_kernels.hip")).read()
+CSRC = os.path.join(ROOT, "simd_dct_amd", "csrc")
+PASSES = open(os.path.join(CSRC, "aan_passes.h")).read()  # the four passes and the macros of their blocks
+KERNELS = open(os.path.join(CSRC, "mdct_kernels.hip")).read()  # quant_dequant8
 
 
 # ---- expression trees
@@ -70,7 +74,7 @@ MACROS = {"MDCT_SUB": ' neg_lo:[0,1] neg_hi:[0,1]\\n\\t', "MDCT_KLO": ' op_sel:[
 
 def test_the_macros_above_are_the_source_s():
     for k, v in MACROS.items():
-        line = next(ln for ln in SRC.splitlines() if ln.startswith("#define %s " % k))
+        line = next(ln for ln in PASSES.splitlines() if ln.startswith("#define %s " % k))
         text = line[line.index('"') + 1:]
         assert text[:text.index('"')] == v, k
 
@@ -85,8 +89,8 @@ def parse_line(line):
 
 
 def blocks_of(func):
-    body = SRC[SRC.index("void %s(" % func):]
-    body = body[body.index("#else"):body.index("#endif")]
+    body = PASSES[PASSES.index("void %s(" % func):]
+    body = body[:re.search(r"\n}\n", body).end()]  # to the function's closing brace: the next definition starts after it
     out = []
     for m in re.finditer(r'asm\((.*?)\n\s*:', body, re.S):
         text = m.group(1)
@@ -153,7 +157,7 @@ def test_column_passes_are_the_scalar_butterflies_on_both_halves():
         regs[9], regs[10] = ks
         run(ins, regs)
         # which register holds which output: the assignments after the block
-        body = SRC[SRC.index("void %s(" % func):]
+        body = PASSES[PASSES.index("void %s(" % func):]
         tail = re.search(r"p\[0\] = (\w+); p\[1\] = (\w+); p\[2\] = (\w+); p\[3\] = (\w+); p\[4\] = (\w+); p\[5\] = (\w+); p\[6\] = (\w+); p\[7\] = (\w+);", body)
         where = [8 if r == "T" else int(r[1]) for r in tail.groups()]
         assert sorted(where) != list(range(8)) or True
@@ -217,7 +221,7 @@ def test_quantise_dequantise_block():
 
 
 def blocks_of_quant():
-    body = SRC[SRC.index("void quant_dequant8("):]
+    body = KERNELS[KERNELS.index("void quant_dequant8("):]
     body = body[:body.index("#undef MDCT_Q8")]
     m = re.search(r'asm\((.*?)\n\s*:', body, re.S)
     text = m.group(1)
@@ -231,3 +235,13 @@ def blocks_of_quant():
             continue
         ins.append(parse_line(line))
     return [ins]
+
+
+def test_the_proven_text_is_the_only_text():
+    """every proven function has ONE definition in csrc/, and no translation unit compiles another's text"""
+    texts = {f: open(f).read() for f in sorted(glob.glob(os.path.join(CSRC, "*")))}
+    assert len(texts) > 13
+    for func in ("aan_fwd_v", "aan_inv_v", "aan_fwd_h", "aan_inv_h", "quant_dequant8"):
+        assert sum(t.count("void %s(" % func) for t in texts.values()) == 1, func
+    for f, t in texts.items():
+        assert not re.search(r'#\s*include\s*"[^"\n]*\.hip"', t), f
