@@ -1,6 +1,6 @@
 # Top-level build for C/C++ users (the Python entry point __graft_entry__.build() does the same).
 #   make            libmdct_hip.so + the C++ CLI + the CPU checker
-#   make lib | cli | jpeg_example | jpegcoef | oracle | ref | clean
+#   make lib | cli | jpeg_example | jpegcoef | jpegprog | oracle | ref | clean
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := simd_dct_amd/csrc
@@ -39,6 +39,11 @@ simd_dct_amd/libmdct_jpegenc_opt.so: $(CSRC)/jpeg_encode_opt.hip $(HEADERS) $(LI
 simd_dct_amd/libmdct_jpegcoef.so: $(CSRC)/jpeg_coef.hip $(HEADERS) simd_dct_amd/libmdct_jpegenc_opt.so
 	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_jpegenc_opt -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
 
+# the scans of a progressive file from coefficient planes (include/mdct_jpegprog.h)
+jpegprog: simd_dct_amd/libmdct_jpegprog.so
+simd_dct_amd/libmdct_jpegprog.so: $(CSRC)/jpeg_progressive.hip $(HEADERS) simd_dct_amd/libmdct_jpegenc_opt.so
+	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_jpegenc_opt -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
+
 oracle:
 	$(MAKE) -C oracle
 ref:
@@ -48,4 +53,4 @@ clean:
 	rm -f $(LIB) tools/simd_dct_cli tools/mdct_jpeg
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib cli jpeg_example jpegcoef oracle ref clean
+.PHONY: all lib cli jpeg_example jpegcoef jpegprog oracle ref clean

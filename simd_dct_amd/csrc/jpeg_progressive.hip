@@ -1,0 +1,662 @@
+// jpeg_progressive.hip -- the scans of a progressive JPEG with spectral selection, Ah = Al = 0 (include/mdct_jpegprog.h; ITU-T T.81
+// Annex G.1.2): quantised coefficient planes -> the Huffman segments of the DC-first scan and of the scans of
+// one AC band of one component with end-of-band runs, and their symbol statistics.
+//
+// Built into its own library, libmdct_jpegprog.so, linked against libmdct_hip.so (launch tally) and libmdct_jpegenc_opt.so (segment
+// stride).
+//
+// k_prog_dc<H, V, STATS> is k_coef (jpeg_coef.hip) with a source that fetches the DC level alone: the kernel body is opt_symbols.h's
+// with no AC entries and no EOB (HuffSeqCoder16::chunk with n = 0), the lane-to-block layout scan_chunks.h's ChunkGrid.
+//
+// k_prog_ac<STATS>: one workgroup of 4 waves per block row, chunks of 256 blocks, lane = block in both phases.
+//   fetch    the lane's 8 rows (the fetch of CoefChunks), the levels of zig-zag positions ss..se compacted into its LDS row as
+//            run << 12 | level entries; zeros outside the band are not counted and levels outside it do not appear.  Two flags per
+//            block: non-empty (an entry) and tail (position se is zero); each wave leaves its two 64-bit ballots in LDS.
+//   EOB run  the run pending before a non-empty block, and the ordinal of a tail block in its stretch, follow from the nearest
+//            non-empty block before it: found in the wave's own mask, else in the earlier waves' masks, else the stretch began
+//            before the chunk and the count carried in (uniform over the workgroup, kept mod 32767) is added.  No lane waits for
+//            another.  A non-empty block codes EOBn of (pending mod 32767) in front of its entries; the tail block whose ordinal
+//            reaches 32767 codes the full run (0xE0 and 14 one-bits) itself.
+//   symbols  the token's bits join the lane's bit count; the scan of the counts, the ring, the 0xFF count and finish are
+//            HuffSeqCoder16's (BandCoder below).  After the last chunk one lane writes the run still pending.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "aan_passes.h" // of it, compact_levels16 (k_prog_dc, through ChunkGrid) and kZigZag
+#include "host_error.h"
+#include "coef_host.h"
+#include "launch_tally.h"
+#include "mdct_jpegprog.h"
+#include "scan_chunks.h"
+#include "opt_symbols.h"
+#include "scan_host.h"
+#include "wg_sync.h"
+
+namespace mdct
+{
+namespace jpegprog
+{
+
+using namespace scan_order;
+using opt_symbols::kRing;
+
+// ---------------------------------------------------------------------------------------------------------------------- the DC scan
+struct DcArgs
+{
+  const int16_t *coef[3];
+  size_t pitch[3]; // elements
+  uint8_t *out;    // segments, seg_stride apart, indexed by the interval
+  uint32_t *seg_bytes, *ff_counts;
+  uint32_t *hist;            // STATS: [2][272]
+  uint32_t *uncoded;         // coder: symbols without a code
+  uint32_t *unrepresentable; // DC differences that had to be clamped
+  size_t seg_stride;
+  uint32_t mcus_x, my0;
+  uint32_t cls0;       // one plane: its class in the histogram
+  uint32_t complete;   // coder: every DC category has a code
+  uint32_t dc[2][12];  // size << 16 | code per DC category, 0: no code; one plane: its table in [0]
+  uint32_t ac[2][256]; // all zero: the body's AC tables, never looked up
+};
+static_assert(sizeof(DcArgs) <= 4096, "kernel argument block");
+
+// The DC source of the chunk skeleton (scan_chunks.h): one 16-bit load per block.
+template <int H, int V, class Args>
+struct DcChunks : ChunkGrid<H, V, Args>
+{
+  using Grid = ChunkGrid<H, V, Args>;
+  using Grid::a;
+  using Grid::bx0;
+  using Grid::last_blk;
+  using Grid::M;
+  using Grid::meta;
+  using Grid::step;
+  using Grid::tid;
+  static constexpr bool kCountsLoss = true;
+
+  const int16_t *src_row;
+  int16_t level;
+  uint32_t lost = 0; // no AC level is read
+
+  __device__ __forceinline__ explicit DcChunks(const Args &a_) : Grid(a_) {}
+
+  __device__ __forceinline__ void fetch(uint32_t bx) { level = src_row[(size_t)min(bx, last_blk) * 8]; }
+
+  __device__ __forceinline__ void init(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[Grid::kThreads])
+  {
+    uint32_t comp, brow;
+    bool chroma_wave;
+    Grid::place(tid_, lane, wave, my, rec_all, meta_, comp, brow, chroma_wave);
+    const size_t pitch0 = a.pitch[0], pitch1 = a.pitch[1], pitch2 = a.pitch[2];
+    const int16_t *const c0 = a.coef[0], *const c1 = a.coef[1], *const c2 = a.coef[2];
+    src_row = (comp == 0 ? c0 : comp == 1 ? c1 : c2) + (size_t)brow * 8 * (comp == 0 ? pitch0 : comp == 1 ? pitch1 : pitch2);
+    fetch(bx0);
+  }
+
+  // the DC level alone in meta[par][tid]: no entries, no EOB; then the next chunk's level is requested
+  __device__ __forceinline__ void transform(uint32_t m0, uint32_t chunk, uint32_t par)
+  {
+    meta[par][tid] = (uint32_t)(uint16_t)level;
+    if (m0 + M < a.mcus_x)
+      fetch(bx0 + (chunk + 1) * step);
+  }
+};
+
+template <int H, int V, bool STATS>
+__global__ __launch_bounds__((64 * kWaves<H, V>)) void k_prog_dc(DcArgs a)
+{
+  opt_symbols::opt_kernel_body<DcChunks<H, V, DcArgs>, H, V, STATS>(a);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------- an AC band
+struct BandArgs
+{
+  const int16_t *coef;
+  size_t pitch; // elements
+  uint8_t *out;
+  uint32_t *seg_bytes, *ff_counts;
+  uint32_t *hist; // STATS: [256]
+  uint32_t *uncoded, *unrepresentable;
+  size_t seg_stride;
+  uint32_t blocks_x, by0;
+  uint32_t ss, se;
+  uint32_t complete; // coder: every symbol of a band scan has a code
+  uint32_t ac[256];  // size << 16 | code per RRRRSSSS, 0: no code
+};
+static_assert(sizeof(BandArgs) <= 4096, "kernel argument block");
+
+constexpr uint32_t kBandWaves = 4, kBandThreads = 64 * kBandWaves;
+constexpr uint32_t kFullRun = 0x7FFF; // the run that is emitted at once (EOB14 with 14 one-bits)
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// an end-of-band run 1..32767 -> RRRRSSSS = n << 4, and the n low bits of the run that follow the code
+__device__ __forceinline__ void eob_run_symbol(uint32_t run, uint32_t &sym, uint32_t &extra, uint32_t &n)
+{
+  n = 31u - (uint32_t)__builtin_clz(run);
+  sym = n << 4;
+  extra = run & ((1u << n) - 1u);
+}
+
+// The run after block I of the chunk (0 where that block is no tail block; I = -1: the run carried in), not yet reduced mod 32767:
+// ne / tl are the waves' ballots of non-empty and tail blocks.
+__device__ __forceinline__ uint32_t run_after(int I, uint32_t carry, const unsigned long long *ne, const unsigned long long *tl)
+{
+  if (I < 0)
+    return carry;
+  int w = I >> 6;
+  unsigned long long m = ne[w] & (~0ull >> (63 - (I & 63)));
+#pragma unroll
+  for (int k = 0; k < (int)kBandWaves - 1; k++)
+    if (m == 0 && w > 0)
+      m = ne[--w];
+  if (m == 0)
+    return carry + (uint32_t)I + 1u;
+  const int j = 63 - __builtin_clzll(m);
+  return (uint32_t)(I - (w * 64 + j)) + (uint32_t)((tl[w] >> j) & 1ull);
+}
+
+// HuffSeqCoder16 for a band: no DC token; an optional run token (code of `sym`, then n_extra bits) in front of the lane's entries, no
+// EOB behind them.  State, scan, ring, 0xFF count and finish are the base's.
+struct BandCoder : HuffSeqCoder16<(int)kBandWaves, kRing>
+{
+  __device__ __forceinline__ void chunk_band(const uint16_t *rec, int n, bool live, bool has_run, uint32_t sym, uint32_t extra, uint32_t n_extra, const uint32_t *ac)
+  {
+    constexpr uint32_t RING = kRing;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t *rec2 = reinterpret_cast<const uint32_t *>(rec);
+    const uint32_t run_code = ac[sym & 0xFFu];
+    uint32_t bits = 0;
+    if (live)
+    {
+      if (has_run)
+        bits = (run_code >> 16) + n_extra;
+      for (int i = 0; i < n; i += 2)
+      {
+        const uint32_t w = rec2[i >> 1];
+        bits += huff_ac_token12(w & 0xFFFFu, ac).len;
+        if (i + 1 < n)
+          bits += huff_ac_token12(w >> 16, ac).len;
+      }
+    }
+    uint32_t incl = bits;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+    {
+      const uint32_t v = __shfl_up(incl, d, 64);
+      if (lane >= (uint32_t)d)
+        incl += v;
+    }
+    if (lane == 63)
+      tot[par][wave] = incl;
+    wg_sync(); // also: every wave has flushed (and cleared) the previous chunk's words
+    uint32_t wave_start = 0, chunk_bits = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBandWaves; w++)
+    {
+      const uint32_t t = tot[par][w];
+      wave_start += w < wave ? t : 0;
+      chunk_bits += t;
+    }
+    const uint32_t end_bits = base_bits + chunk_bits;
+    const uint32_t w_first = base_bits >> 5, w_end = end_bits >> 5;
+    for (uint32_t win = w_first; win <= w_end; win += RING)
+    {
+      if (win != w_first)
+        wg_sync(); // the previous window's slots are cleared and the clearing ds_writes have landed (HuffRowCoder16, wg_sync.h)
+      if (live)
+      {
+        const uint32_t cur = base_bits + wave_start + (incl - bits);
+        uint32_t widx = cur >> 5;
+        uint32_t acc = 0;
+        uint32_t nacc = cur & 31;
+        auto put = [&](uint32_t tok, uint32_t len) { // len <= 27, tok < 2^len
+          const uint32_t total = nacc + len;
+          if (total < 32)
+          {
+            acc = (acc << len) | tok;
+            nacc = total;
+          }
+          else
+          {
+            const uint32_t over = total - 32;
+            if (widx - win < RING)
+              atomicOr(&ring[widx & (RING - 1)], (acc << ((32 - nacc) & 31)) | (tok >> over));
+            widx++;
+            acc = tok & ((1u << over) - 1u);
+            nacc = over;
+          }
+        };
+        if (has_run)
+        {
+          put(run_code & 0xFFFFu, run_code >> 16);
+          put(extra, n_extra);
+        }
+        for (int i = 0; i < n; i += 2)
+        {
+          const uint32_t w = rec2[i >> 1];
+          const HuffTok ta = huff_ac_token12(w & 0xFFFFu, ac);
+          put(ta.bits, ta.len);
+          if (i + 1 < n)
+          {
+            const HuffTok tb = huff_ac_token12(w >> 16, ac);
+            put(tb.bits, tb.len);
+          }
+        }
+        if (nacc && widx - win < RING)
+          atomicOr(&ring[widx & (RING - 1)], acc << (32 - nacc));
+      }
+      wg_sync();
+      const uint32_t stop = min(w_end, win + RING);
+      for (uint32_t w = win + tid; w < stop; w += kBandThreads)
+      {
+        const uint32_t v = ring[w & (RING - 1)];
+        ff += (uint32_t)__builtin_popcount(ff_bytes(v));
+        out_w[w] = __builtin_bswap32(v);
+        ring[w & (RING - 1)] = 0;
+      }
+    }
+    base_bits = end_bits;
+    par ^= 1;
+  }
+
+  // one thread, after the last chunk (behind a workgroup barrier) and before finish: the run still pending, at most 16 + 14 bits.  The
+  // ring's slot of the last, incomplete word holds its bits and the slot after it is clear.
+  __device__ __forceinline__ void flush_run(uint32_t code, uint32_t extra, uint32_t n_extra)
+  {
+    const unsigned long long tok = (unsigned long long)(code & 0xFFFFu) << n_extra | extra;
+    const uint32_t len = (code >> 16) + n_extra, wi = base_bits >> 5, off = base_bits & 31;
+    if (len == 0)
+      return;
+    unsigned long long two = (unsigned long long)ring[wi & (kRing - 1)] << 32 | ring[(wi + 1) & (kRing - 1)];
+    two |= tok << (64 - off - len); // off + len <= 31 + 30
+    ring[wi & (kRing - 1)] = (uint32_t)(two >> 32);
+    ring[(wi + 1) & (kRing - 1)] = (uint32_t)two;
+    base_bits += len;
+    if ((base_bits >> 5) > wi)
+    { // the word is complete
+      const uint32_t v = (uint32_t)(two >> 32);
+      ff += (uint32_t)__builtin_popcount(ff_bytes(v));
+      out_w[wi] = __builtin_bswap32(v);
+    }
+  }
+};
+
+template <bool STATS>
+__global__ __launch_bounds__(kBandThreads) void k_prog_ac(BandArgs a)
+{
+  __shared__ uint32_t ac[STATS ? 1 : 256];
+  __shared__ __attribute__((aligned(16))) uint16_t rec_all[kBandThreads * kRec16Row];
+  __shared__ unsigned long long ne[kBandWaves], tl[kBandWaves]; // the waves' ballots of non-empty and of tail blocks
+  __shared__ uint32_t ring[STATS ? 1 : kRing];
+  __shared__ uint32_t tot[2][kBandWaves];
+  __shared__ uint32_t ff_total;
+  __shared__ uint32_t hist[STATS ? kBandWaves : 1][STATS ? 256 : 1]; // one histogram per wave
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t by = a.by0 + blockIdx.x;
+  const uint32_t ss = a.ss, se = a.se, last_blk = a.blocks_x - 1;
+  BandCoder coder;
+  if constexpr (STATS)
+  {
+    for (uint32_t i = tid; i < kBandWaves * 256; i += kBandThreads)
+      (&hist[0][0])[i] = 0;
+  }
+  else
+  {
+    ac[tid] = a.ac[tid];
+    if (tid == 0)
+      ff_total = 0;
+    for (uint32_t w = tid; w < kRing; w += kBandThreads)
+      ring[w] = 0;
+    coder.ring = ring;
+    coder.tot = tot;
+    coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)by * a.seg_stride);
+  }
+  uint16_t *rec = rec_all + tid * kRec16Row;
+  uint32_t *whist = hist[STATS ? wave : 0];
+  const size_t pitch = a.pitch;
+  const int16_t *src_row = a.coef + (size_t)by * 8 * pitch;
+  uint4 rows[8];
+  // the 8 rows of block min(bx, last) of the block row (lanes past the row's end redo the last block); streamed once
+  auto fetch = [&](uint32_t bx) {
+    const int16_t *src = src_row + (size_t)min(bx, last_blk) * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+    {
+      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + (size_t)r * pitch));
+      rows[r] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+  };
+  fetch(tid);
+  uint32_t carry = 0;   // the run pending after the chunks so far, mod 32767; uniform
+  uint32_t lost = 0, uncoded = 0;
+  wg_sync(); // the table and the cleared ring / histograms
+  for (uint32_t m0 = 0; m0 < a.blocks_x; m0 += kBandThreads)
+  {
+    const bool live = m0 + tid <= last_blk;
+    // ---- levels of the band -> entries (compact_levels16 with the band's bounds; AC clamped to +-1023 and counted)
+    int val[64];
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+    {
+      const uint32_t w[4] = {rows[r].x, rows[r].y, rows[r].z, rows[r].w};
+#pragma unroll
+      for (int u = 0; u < 8; u++)
+        val[r * 8 + u] = (u & 1) ? (int)w[u >> 1] >> 16 : (int)(int16_t)(w[u >> 1] & 0xFFFFu);
+    }
+    uint32_t pos = 0, r12 = 0, clamped = 0;
+    bool se_coded = false;
+#pragma unroll
+    for (int k = 1; k < 64; k++)
+    {
+      const bool in = (uint32_t)k >= ss && (uint32_t)k <= se;
+      const int l = val[kZigZag[k]];
+      const int c = l > 1023 ? 1023 : (l < -1023 ? -1023 : l);
+      const bool nz = in && l != 0;
+      clamped += (in && c != l) ? 1u : 0u;
+      const bool wr = nz || (in && r12 == 0xF000u);
+      rec[pos] = (uint16_t)(((uint32_t)c & 0xFFFu) | r12);
+      pos += wr ? 1u : 0u;
+      r12 = wr ? 0u : (in ? r12 + 0x1000u : r12);
+      se_coded = se_coded || ((uint32_t)k == se && nz);
+    }
+    uint32_t n_all = pos;
+#pragma unroll
+    for (int t = 0; t < 3; t++) // ZRL entries after the last level become part of the end of band
+      n_all -= (n_all > 0 && rec[n_all - 1] == 0xF000u) ? 1u : 0u;
+    const int n = live ? (int)n_all : 0;
+    lost += live ? clamped : 0u;
+    const bool nonempty = n > 0, tail = live && !se_coded;
+    const unsigned long long bne = __ballot(nonempty), btl = __ballot(tail);
+    if (lane == 0)
+    {
+      ne[wave] = bne;
+      tl[wave] = btl;
+    }
+    if (m0 + kBandThreads < a.blocks_x)
+      fetch(m0 + kBandThreads + tid);
+    wg_sync(); // the ballots of every wave
+    // ---- the end-of-band run in front of this block
+    const uint32_t r = run_after(nonempty ? (int)tid - 1 : (int)tid, carry, ne, tl);
+    const uint32_t r_end = run_after((int)min(kBandThreads - 1, last_blk - m0), carry, ne, tl);
+    bool has_run = false;
+    uint32_t sym = 0, extra = 0, n_extra = 0;
+    if (nonempty)
+    {
+      const uint32_t p = r >= kFullRun ? r - kFullRun : r;
+      has_run = p != 0;
+      if (has_run)
+        eob_run_symbol(p, sym, extra, n_extra);
+    }
+    else if (live && r == kFullRun)
+    {
+      has_run = true;
+      eob_run_symbol(kFullRun, sym, extra, n_extra);
+    }
+    carry = r_end >= kFullRun ? r_end - kFullRun : r_end;
+    if constexpr (STATS)
+    {
+      if (has_run)
+        atomicAdd(&whist[sym], 1u);
+      // a symbol that many lanes hold at once: one add per wave
+      auto add_ballot = [&](bool p, uint32_t s) {
+        const uint32_t c = (uint32_t)__popcll(__ballot(p));
+        if (lane == 0 && c)
+          atomicAdd(&whist[s], c);
+      };
+      for (int i = 0; __ballot(i < n) != 0; i++)
+      { // the lanes' i-th entries together
+        const bool on = i < n;
+        const uint32_t s = on ? opt_symbols::ac_symbol12(rec[i]) : 0xFFFFu;
+        add_ballot(s == 0x01u, 0x01u);
+        add_ballot(s == 0x02u, 0x02u);
+        add_ballot(s == 0x11u, 0x11u);
+        if (on && s != 0x01u && s != 0x02u && s != 0x11u)
+          atomicAdd(&whist[s], 1u);
+      }
+      wg_sync(); // every lane has read the ballots: the next chunk may write them (the coder's barriers)
+    }
+    else
+    {
+      if (!a.complete)
+      { // the symbols this block needs that the table does not code
+        if (has_run)
+          uncoded += (ac[sym] >> 16) == 0 ? 1u : 0u;
+        for (int i = 0; i < n; i++)
+          uncoded += (ac[opt_symbols::ac_symbol12(rec[i])] >> 16) == 0 ? 1u : 0u;
+      }
+      coder.chunk_band(rec, n, live, has_run, sym, extra, n_extra, ac);
+    }
+  }
+  // ---- the run still pending ends with the interval
+  uint32_t sym = 0, extra = 0, n_extra = 0;
+  if (carry)
+    eob_run_symbol(carry, sym, extra, n_extra);
+  if (lost)
+    atomicAdd(a.unrepresentable, lost);
+  if constexpr (STATS)
+  {
+    if (tid == 0 && carry)
+      atomicAdd(&whist[sym], 1u);
+    wg_sync();
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBandWaves; w++)
+      s += hist[w][tid];
+    if (s)
+      atomicAdd(&a.hist[tid], s);
+  }
+  else
+  {
+    if (tid == 0 && carry && !a.complete)
+      uncoded += (ac[sym] >> 16) == 0 ? 1u : 0u;
+    if (uncoded)
+      atomicAdd(a.uncoded, uncoded);
+    wg_sync(); // every wave has flushed and cleared the last chunk's words
+    if (tid == 0 && carry)
+      coder.flush_run(ac[sym], extra, n_extra); // a word it completes joins this thread's 0xFF count, added below
+    if (coder.ff)
+      atomicAdd(&ff_total, coder.ff);
+    wg_sync();
+    if (tid == 0)
+    {
+      uint32_t ff_last;
+      a.seg_bytes[by] = coder.finish(&ff_last);
+      a.ff_counts[by] = ff_total + ff_last;
+    }
+  }
+}
+
+} // namespace jpegprog
+} // namespace mdct
+
+using namespace mdct::jpegprog;
+using mdct::opt_symbols::kHist;
+
+namespace
+{
+
+static_assert(mdct::opt_symbols::kClass == MDCT_JPEGENC_OPT_HIST_CLASS, "counts per class");
+
+// the planes of a DC scan: one, or three on one MCU grid (the samplings mdct_jpegcoef_scan_rows takes); *h = 0: one plane
+int check_dc_planes(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, int *h, int *v, uint32_t *per_row, uint32_t *n_rows)
+{
+  if (interleaved != 0 && interleaved != 1)
+    return fail(MDCT_INVALID_PARAMETER, "interleaved %d (0 or 1)", interleaved);
+  if (n_planes != (interleaved ? 3 : 1))
+    return fail(MDCT_INVALID_PARAMETER, "%d planes (interleaved = 0 takes one, interleaved = 1 takes Y, Cb, Cr)", n_planes);
+  if (interleaved)
+    return check_coef_mcu_planes(planes, h, v, per_row, n_rows);
+  *h = *v = 0;
+  *per_row = planes[0].blocks_x;
+  *n_rows = planes[0].blocks_y;
+  return check_coef_plane(planes[0], "plane", 0);
+}
+
+int check_band(int ss, int se)
+{
+  if (ss < 1 || se > 63 || ss > se)
+    return fail(MDCT_INVALID_PARAMETER, "band %d..%d (1 <= ss <= se <= 63)", ss, se);
+  return MDCT_SUCCESS;
+}
+
+int launched()
+{
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MDCT_SUCCESS : fail(MDCT_NOT_SUPPORTED, "launch: %s", hipGetErrorString(e));
+}
+
+template <bool STATS>
+int launch_dc(const DcArgs &a, int h, int v, unsigned n_intervals, hipStream_t s)
+{
+  const dim3 grid(n_intervals);
+  if (h == 0)
+    MDCT_LAUNCH((k_prog_dc<0, 0, STATS>), grid, dim3(64 * kWaves<0, 0>), 0, s, a);
+  else if (h == 1)
+    MDCT_LAUNCH((k_prog_dc<1, 1, STATS>), grid, dim3(64 * kWaves<1, 1>), 0, s, a);
+  else if (v == 1)
+    MDCT_LAUNCH((k_prog_dc<2, 1, STATS>), grid, dim3(64 * kWaves<2, 1>), 0, s, a);
+  else
+    MDCT_LAUNCH((k_prog_dc<2, 2, STATS>), grid, dim3(64 * kWaves<2, 2>), 0, s, a);
+  return launched();
+}
+
+void dc_planes(DcArgs &a, const mdct_jpegcoef_plane *planes, int n_planes, uint32_t per_row)
+{
+  for (int c = 0; c < n_planes; c++)
+  {
+    a.coef[c] = planes[c].coef;
+    a.pitch[c] = planes[c].pitch;
+  }
+  a.mcus_x = per_row;
+}
+
+void band_plane(BandArgs &a, const mdct_jpegcoef_plane &p, int ss, int se)
+{
+  a.coef = p.coef;
+  a.pitch = p.pitch;
+  a.blocks_x = p.blocks_x;
+  a.ss = (uint32_t)ss;
+  a.se = (uint32_t)se;
+}
+
+} // namespace
+
+extern "C" {
+
+const char *mdct_jpegprog_last_error(void) { return g_err; }
+
+int mdct_jpegprog_dc_stats(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, int cls, uint32_t *hist, uint32_t *unrepresentable, void *stream)
+{
+  if (!planes || !hist || !unrepresentable)
+    return fail(MDCT_INVALID_PARAMETER, "null planes / hist / unrepresentable");
+  if (cls != 0 && cls != 1)
+    return fail(MDCT_INVALID_PARAMETER, "class %d (0 luminance, 1 chrominance)", cls);
+  int rc, h, v;
+  uint32_t per_row, n_rows;
+  if ((rc = check_word(hist, "hist")) || (rc = check_word(unrepresentable, "unrepresentable")) || (rc = check_dc_planes(planes, n_planes, interleaved, &h, &v, &per_row, &n_rows)))
+    return rc;
+  DcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hist = hist;
+  a.unrepresentable = unrepresentable;
+  a.cls0 = (uint32_t)cls;
+  dc_planes(a, planes, n_planes, per_row);
+  const hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * kHist, s);
+  if (e != hipSuccess)
+    return fail(MDCT_NOT_SUPPORTED, "memset: %s", hipGetErrorString(e));
+  return launch_dc<true>(a, h, v, n_rows, s);
+}
+
+int mdct_jpegprog_dc_rows(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, const mdct_jpegenc_opt_spec *specs, size_t r0, size_t r1, uint8_t *out,
+                          size_t seg_stride, uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream)
+{
+  if (!planes || !specs || !out || !seg_bytes || !ff_counts || !uncoded || !unrepresentable)
+    return fail(MDCT_INVALID_PARAMETER, "null planes / specs / out / seg_bytes / ff_counts / uncoded / unrepresentable");
+  int rc, h, v;
+  uint32_t per_row, n_rows;
+  if ((rc = check_dc_planes(planes, n_planes, interleaved, &h, &v, &per_row, &n_rows)))
+    return rc;
+  if (r0 >= r1 || r1 > n_rows)
+    return fail(MDCT_INVALID_PARAMETER, "intervals [%zu, %zu) of %u", r0, r1, n_rows);
+  const size_t blocks = (size_t)per_row * (size_t)(h ? h * v + 2 : 1);
+  if ((rc = check_seg_stride(seg_stride, out, mdct_jpegenc_opt_seg_stride(blocks), 209, blocks, "interval", "the stride of the table-taking coders")))
+    return rc;
+  if ((rc = check_word(uncoded, "uncoded")) || (rc = check_word(unrepresentable, "unrepresentable")))
+    return rc;
+  DcArgs a;
+  memset(&a, 0, sizeof(a));
+  bool complete = true;
+  static const char *const names[2] = {"DC specification", "DC chrominance specification"};
+  for (int w = 0; w < (h ? 2 : 1); w++)
+    if ((rc = spec_codes(&specs[w], false, names[w], a.dc[w], &complete)))
+      return rc;
+  a.complete = complete;
+  dc_planes(a, planes, n_planes, per_row);
+  a.out = out;
+  a.seg_bytes = seg_bytes;
+  a.ff_counts = ff_counts;
+  a.uncoded = uncoded;
+  a.unrepresentable = unrepresentable;
+  a.seg_stride = seg_stride;
+  a.my0 = (uint32_t)r0;
+  return launch_dc<false>(a, h, v, (unsigned)(r1 - r0), (hipStream_t)stream);
+}
+
+int mdct_jpegprog_ac_stats(const mdct_jpegcoef_plane *plane, int ss, int se, uint32_t *hist, uint32_t *unrepresentable, void *stream)
+{
+  if (!plane || !hist || !unrepresentable)
+    return fail(MDCT_INVALID_PARAMETER, "null plane / hist / unrepresentable");
+  int rc;
+  if ((rc = check_word(hist, "hist")) || (rc = check_word(unrepresentable, "unrepresentable")) || (rc = check_coef_plane(*plane, "plane", 0)) || (rc = check_band(ss, se)))
+    return rc;
+  BandArgs a;
+  memset(&a, 0, sizeof(a));
+  band_plane(a, *plane, ss, se);
+  a.hist = hist;
+  a.unrepresentable = unrepresentable;
+  const hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * 256, s);
+  if (e != hipSuccess)
+    return fail(MDCT_NOT_SUPPORTED, "memset: %s", hipGetErrorString(e));
+  MDCT_LAUNCH((k_prog_ac<true>), dim3(plane->blocks_y), dim3(kBandThreads), 0, s, a);
+  return launched();
+}
+
+int mdct_jpegprog_ac_rows(const mdct_jpegcoef_plane *plane, int ss, int se, size_t by0, size_t by1, const mdct_jpegenc_opt_spec *ac, uint8_t *out, size_t seg_stride,
+                          uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream)
+{
+  if (!plane || !out || !seg_bytes || !ff_counts || !uncoded || !unrepresentable)
+    return fail(MDCT_INVALID_PARAMETER, "null plane / out / seg_bytes / ff_counts / uncoded / unrepresentable");
+  int rc;
+  if ((rc = check_coef_plane(*plane, "plane", 0)) || (rc = check_band(ss, se)))
+    return rc;
+  if (by0 >= by1 || by1 > plane->blocks_y)
+    return fail(MDCT_INVALID_PARAMETER, "block rows [%zu, %zu) of %u", by0, by1, plane->blocks_y);
+  if ((rc = check_seg_stride(seg_stride, out, mdct_jpegenc_opt_seg_stride(plane->blocks_x), 209, plane->blocks_x, "row", "1668 bits per block")))
+    return rc;
+  if ((rc = check_word(uncoded, "uncoded")) || (rc = check_word(unrepresentable, "unrepresentable")))
+    return rc;
+  BandArgs a;
+  memset(&a, 0, sizeof(a));
+  bool all = true;
+  if ((rc = spec_codes(ac, true, "AC specification", a.ac, &all)))
+    return rc;
+  for (int n = 1; n < 15; n++) // and the EOBn of a band scan
+    all = all && a.ac[n << 4];
+  a.complete = all;
+  band_plane(a, *plane, ss, se);
+  a.out = out;
+  a.seg_bytes = seg_bytes;
+  a.ff_counts = ff_counts;
+  a.uncoded = uncoded;
+  a.unrepresentable = unrepresentable;
+  a.seg_stride = seg_stride;
+  a.by0 = (uint32_t)by0;
+  MDCT_LAUNCH((k_prog_ac<false>), dim3((unsigned)(by1 - by0)), dim3(kBandThreads), 0, (hipStream_t)stream, a);
+  return launched();
+}
+
+} // extern "C"

@@ -108,6 +108,62 @@ def write_jpeg(components, width, height, specs=None, sampling=None, interleaved
     return b"".join(f)
 
 
+def write_progressive_jpeg(qtables, width, height, sampling, scans, *, colorspace=None):
+    """A progressive file (SOF2) with spectral selection only (T.81 Annex G, Ah = Al = 0) around the scans of libmdct_jpegprog.so.
+       qtables: one table per component (64 integers 1..255, natural order); equal tables share an id, in order of appearance
+       sampling: [(h, v)] per component (1 or 3)
+       scans: in file order, dicts with
+         'components': [(component index, td, ta)] -- one component, or all three for an interleaved DC scan
+         'ss', 'se': the band; 0, 0 is the DC scan, an AC band (1 <= ss <= se <= 63) takes one component (G.1.1.1.1)
+         'restart_interval': the scan's DRI, in MCUs (blocks of the component's own grid for one component)
+         'tables': {(table class, id): (bits16, vals)} defined in a DHT in front of the scan (a later scan may redefine an id)
+         'scan': bytes / uint8 array, the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it
+       colorspace: as write_jpeg.
+       Written are SOI, APP0 (or the Adobe APP14), DQT per table, SOF2, and per scan DHT, DRI, SOS and the data; then EOI.  The engine's
+       own reader refuses such a file (read_jpeg: SOF2).  Returns the file as bytes."""
+    zz = api.zigzag_table()
+    nc = len(sampling)
+    if nc not in (1, 3) or len(qtables) != nc:
+        raise ValueError(f"{len(qtables)} tables for {nc} components (1 or 3 of each)")
+    if colorspace not in (None, "grey", "YCbCr", "RGB") or (colorspace == "grey") != (nc == 1 and colorspace is not None):
+        raise ValueError(f"colorspace {colorspace!r} for {nc} components (None; 'grey' for one; 'YCbCr' or 'RGB' for three)")
+    if any(not (1 <= h <= 4 and 1 <= v <= 4) for h, v in sampling):
+        raise ValueError(f"sampling factors {list(sampling)} (1..4)")
+    if colorspace == "RGB":
+        f = [b"\xff\xd8", _seg(0xEE, b"Adobe" + struct.pack(">HHHB", 100, 0, 0, 0))]
+    else:
+        f = [b"\xff\xd8", _seg(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    qts, tq_of = [], []
+    for q in qtables:
+        q = np.asarray(q).reshape(-1)
+        if q.size != 64 or np.any(q != np.rint(q)) or q.min() < 1 or q.max() > 255:
+            raise ValueError("a DQT of 8-bit precision holds 64 integers 1..255")
+        key = [int(x) for x in q]
+        if key not in qts:
+            qts.append(key)
+        tq_of.append(qts.index(key))
+    for tq, q in enumerate(qts):
+        f.append(_seg(0xDB, bytes([tq]) + bytes(q[zz[k]] for k in range(64))))
+    sof = struct.pack(">BHHB", 8, height, width, nc)
+    for ci, (h, v) in enumerate(sampling):
+        sof += bytes([ci + 1, (h << 4) | v, tq_of[ci]])
+    f.append(_seg(0xC2, sof))
+    for k, sc in enumerate(scans):
+        comps, ss, se = list(sc["components"]), int(sc["ss"]), int(sc["se"])
+        if not ((ss == 0 and se == 0 and len(comps) in (1, nc)) or (1 <= ss <= se <= 63 and len(comps) == 1)):
+            raise ValueError(f"scan {k}: band {ss}..{se} of {len(comps)} components (the DC scan is 0..0; an AC band takes one component)")
+        if any(not 0 <= ci < nc or td not in (0, 1) or ta not in (0, 1) for ci, td, ta in comps):
+            raise ValueError(f"scan {k}: components {comps} (index, DC table 0 / 1, AC table 0 / 1)")
+        if not 1 <= int(sc["restart_interval"]) <= 65535:
+            raise ValueError(f"scan {k}: restart interval {sc['restart_interval']} (1..65535)")
+        f.append(_seg(0xC4, b"".join(_dht(tc, th, *spec) for (tc, th), spec in sorted(sc["tables"].items()))))
+        f.append(_seg(0xDD, struct.pack(">H", int(sc["restart_interval"]))))
+        f.append(_seg(0xDA, bytes([len(comps)]) + b"".join(bytes([ci + 1, (td << 4) | ta]) for ci, td, ta in comps) + bytes([ss, se, 0])))
+        f.append(bytes(memoryview(np.ascontiguousarray(sc["scan"]))))
+    f.append(b"\xff\xd9")
+    return b"".join(f)
+
+
 class JpegFormatError(ValueError):
     """a file this reader refuses: malformed, or outside 8-bit baseline / extended-sequential Huffman JPEG with restart markers"""
 

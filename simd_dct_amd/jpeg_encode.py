@@ -332,7 +332,7 @@ def _run_scan(plane, pw, ph, lut, chroma, sc, two_launch, stream, specs=None, un
                              stream=stream)
 
 
-def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True, interleaved=False, optimize=False):
+def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True, interleaved=False, optimize=False, progressive=False):
     """Encode an 8-bit image as a baseline JPEG (JFIF) on the GPU and return the file as bytes.
 
     image: uint8 [H, W, 3] (layout="HWC"), [3, H, W] (layout="CHW") or [H, W] (grey, any layout); a numpy array or CPU tensor is
@@ -356,7 +356,14 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     symbols the coder will emit (symbol_histogram), its 2176 bytes are copied back -- a second wait besides the one for the scan --, the
     tables (one luminance and one chrominance pair, whatever the scan form) are built on the host (optimal_tables), and the coders of
     libmdct_jpegenc_opt.so write the segments with them (two_launch plays no part); the file carries the tables in its DHT segment.
-    DESIGN.md section 4.9.2."""
+    DESIGN.md section 4.9.2.
+
+    progressive=True (a bool): a progressive file (SOF2) with spectral selection, the scans jpeg_transcode.encode_coefficients(
+    progressive=True) writes with its default bands.  The planes are padded to the MCU grid, mdct_fwd_u8_i16
+    with the level shift and the quality tables makes the quantised coefficients the pixel coders are defined on, and the band coders
+    saturate AC levels to +-1023 as the pixel coders do.  The tables are always made for the image: optimize=False is accepted and
+    plays no part, nor does two_launch; interleaved selects the form of the DC scan.  The engine's own decoder does not read the
+    file."""
     import torch
 
     q = _quality(quality)
@@ -364,6 +371,8 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
         raise ValueError(f"interleaved {interleaved!r}: a bool")
     if not isinstance(optimize, (bool, np.bool_)):
         raise ValueError(f"optimize {optimize!r}: a bool")
+    if not isinstance(progressive, (bool, np.bool_)):
+        raise ValueError(f"progressive {progressive!r}: a bool")
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
             raise ValueError(f"image dtype {image.dtype}: uint8")
@@ -380,6 +389,16 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
         image = image.to(dev)
     dev = image.device
     with torch.cuda.device(dev):
+        if progressive:
+            from . import jpeg_progressive
+
+            mcus_x, mcus_y, padded = mcu_grid(W, H, sampling)
+            planes = to_planes(image, subsampling, layout, planes=[torch.empty((ph, pw), dtype=torch.uint8, device=dev) for pw, ph in padded], stream=stream)
+            tabs = [luma] + [chroma] * (len(planes) - 1)
+            coefs = [torch.empty(p.shape, dtype=torch.int16, device=dev) for p in planes]
+            api.u8_i16_batch("fwd", [(p, c, pw, ph, np.asarray(t, dtype=np.float32)) for p, c, (pw, ph), t in zip(planes, coefs, padded, tabs)], level_shift=True, stream=stream)
+            return jpeg_progressive.encode(torch, coefs, tabs, W, H, sampling, mcus_x, mcus_y, None, bool(interleaved) and not grey, jpeg_progressive.check_bands(None, len(planes)),
+                                           stream, saturate=True)
         if interleaved and not grey:
             scan, specs = _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, (luma, chroma), stream, optimize)
             return jfif.write_jpeg([dict(qtable=luma), dict(qtable=chroma), dict(qtable=chroma)], W, H, specs=specs, sampling=sampling, interleaved=scan)

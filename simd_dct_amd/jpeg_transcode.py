@@ -134,8 +134,8 @@ def _pack(torch, seg, counts, stride, rows, pixels, dev, stream):
     return out, off
 
 
-def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=None, optimize=True, interleaved=False, stream=None):
-    """Quantised coefficient planes -> a baseline JPEG file (bytes), without a DCT.
+def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=None, optimize=True, interleaved=False, progressive=False, bands=None, stream=None):
+    """Quantised coefficient planes -> a baseline JPEG file (bytes), or with progressive=True a progressive one, without a DCT.
 
     coefs: 1 or 3 int16 device tensors [rows, columns], each padded to the MCU grid of the frame (jpeg_encode.mcu_grid), in the layout
     decode_jpeg(..., coefficients=True) returns; rows 16-byte aligned.  qtables: one table per component, 64 integers 1..255 in natural
@@ -148,10 +148,25 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
     (jpeg_encode.optimal_tables); False: the Annex K specifications.  Both go through the same coder (coef_rows / coef_scan_rows), then
     the packing launch, a small first buffer and a second packing into the worst case where that did not fit, as encode_jpeg.
     A coefficient that a baseline scan cannot hold (AC outside +-1023, DC difference outside +-2047) raises api.MdctError: no file is
-    returned.  With optimize=True that is known from the statistics launch, before anything is coded."""
+    returned.  With optimize=True that is known from the statistics launch, before anything is coded.
+
+    progressive=True (a bool): a SOF2 file with spectral selection (T.81 Annex G, Ah = Al = 0; jpeg_progressive, DESIGN.md section
+    4.12): the DC scan, then per component the scans of its AC bands with end-of-band runs, every scan with a restart interval per row
+    and its own table.  optimize must be True (the Annex K tables have no codes for the end-of-band runs: ValueError).  interleaved
+    selects the form of the DC scan only: True one interleaved DC scan (the samplings above), False one per component.  bands: per
+    component a list of (ss, se) that tiles 1..63 in order (default: luma (1, 2), (3, 9), (10, 63), chroma (1, 63); grey as luma; anything
+    else is a ValueError); without progressive it must be None.  All statistics launches run first and one copy brings every histogram
+    and the loss count back; then all coding and packing launches, and one copy of the lengths.  The engine's own decoder does not
+    read these files (jfif.read_jpeg refuses SOF2)."""
     import torch
 
     _bools(optimize, interleaved)
+    if not isinstance(progressive, (bool, np.bool_)):
+        raise ValueError(f"progressive {progressive!r}: a bool")
+    if progressive and not optimize:
+        raise ValueError("progressive=True needs optimize=True: the Annex K tables have no codes for end-of-band runs")
+    if bands is not None and not progressive:
+        raise ValueError("bands: only with progressive=True")
     sampling = [(int(h), int(v)) for h, v in sampling]
     nc = len(sampling)
     if nc not in (1, 3) or len(coefs) != nc or len(qtables) != nc:
@@ -162,6 +177,10 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
         raise ValueError(f"image {width}x{height}: 1..65535 each way")
     if interleaved:
         _check_interleaved(sampling)
+    if progressive:
+        from . import jpeg_progressive
+
+        bands = jpeg_progressive.check_bands(bands, nc)
     tabs = []
     for k, q in enumerate(qtables):
         q = np.asarray(q).reshape(-1)
@@ -176,6 +195,10 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
             raise ValueError(f"plane {k}: shape {list(p.shape)}, the MCU grid makes it [{ph}, {pw}]")
         if p.stride(0) % 8 or p.data_ptr() % 16:
             raise ValueError(f"plane {k}: rows must be 16-byte aligned")
+    if progressive:
+        from . import jpeg_progressive
+
+        return jpeg_progressive.encode(torch, coefs, tabs, width, height, sampling, mcus_x, mcus_y, colorspace, bool(interleaved), bands, stream)
     grey = nc == 1
     dev = coefs[0].device
     with torch.cuda.device(dev):
@@ -254,7 +277,7 @@ def plan_transform(width, height, sampling, transform, trim):
     return (size["x"], size["y"]), (size["x"], size["y"]), [(h, v) for h, v in sampling]
 
 
-def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleaved=False, device=None, stream=None):
+def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleaved=False, progressive=False, device=None, stream=None):
     """Rewrite a baseline JPEG without touching its coefficients (jpegtran): decode_coefficients, the optional transform,
     encode_coefficients.  Returns the new file as bytes.
 
@@ -266,6 +289,8 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     interleaved=False: one scan per component, a restart interval per block row; True: one interleaved scan, a restart interval per
     MCU row (three components with 4:4:4, 4:2:2 or 4:2:0 AFTER the transform: ValueError otherwise, before any device work).  Either way
     the output goes through the per-interval decoder ever after, whatever the input's scan form and restart interval were.
+    progressive=True: the output is a progressive file with spectral selection (encode_coefficients: optimize must be True; interleaved
+    selects the form of its DC scan); the engine's own decoder does not read it back.
     The quantisation tables (one per component, equal ones shared) and the colour space (grey, YCbCr, Adobe RGB) survive.
     Blocks of the padded planes beyond a component's own grid are zero after a non-interleaved input; an interleaved output codes them
     as they are -- they are invisible, which is not a loss.
@@ -275,11 +300,15 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     neighbours that were not).
 
     Out of scope: copying EXIF, ICC or comment segments (APPn and COM are dropped but for the colour-space markers); progressive or
-    arithmetic-coded input (read_jpeg refuses both); jpegtran's default of leaving an unmirrored edge strip in place (here: perfect,
+    arithmetic-coded INPUT (read_jpeg refuses both); progressive output with successive approximation; jpegtran's default of leaving an unmirrored edge strip in place (here: perfect,
     trim, or an error); re-quantising (changing quality)."""
     import torch
 
     _bools(optimize, interleaved)
+    if not isinstance(progressive, (bool, np.bool_)):
+        raise ValueError(f"progressive {progressive!r}: a bool")
+    if progressive and not optimize:
+        raise ValueError("progressive=True needs optimize=True: the Annex K tables have no codes for end-of-band runs")
     if transform is not None and transform not in MIRRORED:
         raise ValueError(f"transform {transform!r} (None or one of {', '.join(TRANSFORMS)})")
     info = jfif.read_jpeg(data, require_restart=False)
@@ -306,4 +335,4 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
         if transform in TRANSPOSING:
             qtables = [t.T for t in qtables]
     return encode_coefficients(coefs, [np.rint(t).astype(np.int64).reshape(64) for t in qtables], ow, oh, osampling, colorspace=info["colorspace"],
-                               optimize=bool(optimize), interleaved=bool(interleaved), stream=stream)
+                               optimize=bool(optimize), interleaved=bool(interleaved), progressive=bool(progressive), stream=stream)
