@@ -1,6 +1,6 @@
 # Top-level build for C/C++ users (the Python entry point __graft_entry__.build() does the same).
 #   make            libmdct_hip.so + the C++ CLI + the CPU checker
-#   make lib | cli | jpeg_example | jpegcoef | jpegprog | oracle | ref | clean
+#   make lib | cli | jpeg_example | jpegcoef | jpegprog | jpegdec_prog | oracle | ref | clean
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := simd_dct_amd/csrc
@@ -44,6 +44,13 @@ jpegprog: simd_dct_amd/libmdct_jpegprog.so
 simd_dct_amd/libmdct_jpegprog.so: $(CSRC)/jpeg_progressive.hip $(HEADERS) simd_dct_amd/libmdct_jpegenc_opt.so
 	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_jpegenc_opt -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
 
+# the decoder of a progressive file's scans (include/mdct_jpegdec_prog.h), with the decoder library whose handle and index it takes
+jpegdec_prog: simd_dct_amd/libmdct_jpegdec_prog.so
+simd_dct_amd/libmdct_jpegdec.so: $(CSRC)/jpeg_decode.hip $(HEADERS) $(LIB)
+	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
+simd_dct_amd/libmdct_jpegdec_prog.so: $(CSRC)/jpeg_decode_progressive.hip $(HEADERS) simd_dct_amd/libmdct_jpegdec.so
+	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_jpegdec -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
+
 oracle:
 	$(MAKE) -C oracle
 ref:
@@ -53,4 +60,4 @@ clean:
 	rm -f $(LIB) tools/simd_dct_cli tools/mdct_jpeg
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib cli jpeg_example jpegcoef jpegprog oracle ref clean
+.PHONY: all lib cli jpeg_example jpegcoef jpegprog jpegdec_prog oracle ref clean

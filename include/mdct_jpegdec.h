@@ -13,7 +13,9 @@
  *
  * Scans without restart markers (restart_interval 0, refused here) are decoded by libmdct_jpegdec_unmarked.so
  * (include/mdct_jpegdec_unmarked.h), with the same table handle and descriptor.
- * Out of scope: progressive / arithmetic / 12-bit / lossless JPEG.  Chroma upsampling and colour conversion: include/mdct_jpegcolor.h. */
+ * The scans of a progressive file (spectral selection only, with restart markers) are decoded by libmdct_jpegdec_prog.so
+ * (include/mdct_jpegdec_prog.h), with the same table handle, descriptor and index.
+ * Out of scope: successive approximation / arithmetic / 12-bit / lossless JPEG.  Chroma upsampling and colour conversion: include/mdct_jpegcolor.h. */
 #ifndef MDCT_JPEGDEC_H
 #define MDCT_JPEGDEC_H
 

@@ -1,0 +1,70 @@
+/* mdct_jpegdec_prog.h -- C-ABI of libmdct_jpegdec_prog.so: the scans of a progressive JPEG (SOF2) with spectral selection only
+ * (ITU-T T.81 Annex G, Ah = Al = 0) and restart markers -> quantised int16 coefficient planes on the GPU.
+ *
+ * The reader of what libmdct_jpegprog.so (include/mdct_jpegprog.h) writes.  A progressive file codes every component's coefficients in
+ * several scans: a DC-first scan (ss = se = 0; one component, or all of them interleaved) and AC-band scans (1 <= ss <= se <= 63, one
+ * component each, G.1.1.1.1), whose blocks may end in an end-of-band run (EOBn: this block and run - 1 further ones have no more levels
+ * in the band).  A run never crosses a restart interval (G.1.2.2), so every interval is still independent: one workgroup decodes it,
+ * split across its lanes by self-synchronising sub-sequence decoding, as mdct_jpegdec_decode (include/mdct_jpegdec.h) decodes a
+ * baseline interval.  Table handle, scan descriptor, interval index (mdct_jpegdec_index) and status codes are those of mdct_jpegdec.h.
+ *
+ * Nothing is allocated or synchronised inside mdct_jpegdec_prog_decode: it may be captured into a hipGraph.  Return codes are those of
+ * include/mdct.h; the message of this library's last failure is mdct_jpegdec_prog_last_error().  The library links against
+ * libmdct_jpegdec.so and libmdct_hip.so; its launches appear in mdct_kernel_counts().
+ * Out of scope, refused and never decoded wrongly: successive approximation (Ah or Al != 0: the caller must not hand such a scan
+ * over, the descriptor cannot say it), progressive scans without restart markers, arithmetic coding, 12-bit samples. */
+#ifndef MDCT_JPEGDEC_PROG_H
+#define MDCT_JPEGDEC_PROG_H
+
+#include "mdct_jpegdec.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* one more interval status beside MDCT_JPEGDEC_* (6 is MDCT_JPEGDEC_NOT_SYNCHRONISED of mdct_jpegdec_unmarked.h) */
+#define MDCT_JPEGDEC_EOBRUN_OVERFLOW 7 /* an end-of-band run that reaches past the interval's last block */
+
+/* What the band (ss, se) asks of the descriptor:
+ *   ss == se == 0          a DC-first scan: 1..3 components, interleaved with the descriptor's sampling factors (at most 10 blocks per
+ *                          MCU) or one component with h = v = 1 over its own block grid.  Only dc_slot is used (0..1, present in the
+ *                          table handle); ac_slot is ignored.
+ *   1 <= ss <= se <= 63    an AC-band scan: exactly one component with h = v = 1.  Only ac_slot is used (2..3, present); dc_slot is
+ *                          ignored.
+ * Any other band is MDCT_INVALID_PARAMETER.  Planes, pitch, alignment, the MCU grid, restart_interval > 0 and the limit of 2^31 blocks
+ * are checked as mdct_jpegdec_decode checks them. */
+
+/* number of restart intervals of the scan: ceil(mcus_x * mcus_y / restart_interval); 0 (message set) for anything refused (host
+ * function, no device) */
+size_t mdct_jpegdec_prog_intervals(const mdct_jpegdec_scan *desc, int ss, int se);
+
+/* Decode every restart interval of one scan of the band (ss, se) into the component planes.  scan, scan_len, interval_offsets and
+ * interval_status as for mdct_jpegdec_decode; the offsets come from mdct_jpegdec_index.  One launch, one workgroup per interval.
+ *
+ * What is written:
+ *   a DC-first scan writes position (0, 0) of every block the interval covers (DC predictors reset per interval and component) and
+ *   nothing else;
+ *   an AC-band scan stores the non-zero levels it decodes at their positions inside zig-zag ss..se and nothing else: the caller
+ *   provides planes that are zero in the band (there is no zeroing pass: three band scans of a plane do not each sweep it).
+ * No position outside the band, no block outside the descriptor and no byte outside [scan, scan + scan_len) is touched, whatever the
+ * scan or the offsets hold.
+ *
+ * interval_status: MDCT_JPEGDEC_* per interval, classified as for baseline scans (exactly the interval's blocks, then 1-bit padding,
+ * then RST(k mod 8)); the first error in decoding order.  In an AC band, a level run or a ZRL that moves the index beyond se + 1 (a
+ * ZRL may end exactly at se + 1, as a ZRL may end at 64 in a baseline scan) is COEF_OVERFLOW; an end-of-band run that names more
+ * blocks than the interval has left is EOBRUN_OVERFLOW.
+ * An interval that fails leaves this: the blocks before the failing one hold their levels, exactly; the failing block holds what was
+ * decoded of it before the error (the block in which an overflowing EOBn was met is the failing one; the DC position of a failing
+ * block of a DC scan is not written); in every later block of the interval the band's positions are 0 (position (0, 0) for a DC scan).
+ * Other intervals are not touched by it.  The DC predictor wraps as in mdct_jpegdec_decode: the level stored is (int16_t)pred. */
+int mdct_jpegdec_prog_decode(const mdct_jpegdec_scan *desc, int ss, int se, const mdct_jpegdec_tables *tables, const uint8_t *scan,
+                             size_t scan_len, const uint64_t *interval_offsets, uint32_t *interval_status, void *stream);
+
+/* message of this library's last failure */
+const char *mdct_jpegdec_prog_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MDCT_JPEGDEC_PROG_H */

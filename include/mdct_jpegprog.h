@@ -1,6 +1,7 @@
 /* mdct_jpegprog.h -- C-ABI of libmdct_jpegprog.so: the scans of a progressive JPEG (SOF2) with spectral selection, Ah = Al = 0
  * (ITU-T T.81 Annex G.1.2), coded from quantised coefficient planes: one DC scan, then scans of one band Ss..Se of one component with
- * end-of-band runs.  Successive approximation (refinement scans) is out of scope, and so is reading such files.
+ * end-of-band runs.  Successive approximation (refinement scans) is out of scope.  libmdct_jpegdec_prog.so
+ * (include/mdct_jpegdec_prog.h) decodes these scans back into the planes.
  *
  * A separate library, linked against libmdct_hip.so (include/mdct.h: status codes, launch tally, the packing call) and
  * libmdct_jpegenc_opt.so (include/mdct_jpegenc_opt.h: the specification type, the segment stride, the table maker, which takes the

@@ -119,8 +119,8 @@ def write_progressive_jpeg(qtables, width, height, sampling, scans, *, colorspac
          'tables': {(table class, id): (bits16, vals)} defined in a DHT in front of the scan (a later scan may redefine an id)
          'scan': bytes / uint8 array, the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it
        colorspace: as write_jpeg.
-       Written are SOI, APP0 (or the Adobe APP14), DQT per table, SOF2, and per scan DHT, DRI, SOS and the data; then EOI.  The engine's
-       own reader refuses such a file (read_jpeg: SOF2).  Returns the file as bytes."""
+       Written are SOI, APP0 (or the Adobe APP14), DQT per table, SOF2, and per scan DHT, DRI, SOS and the data; then EOI.
+       read_progressive_jpeg reads such a file back (read_jpeg refuses it, as it refuses every SOF2 file).  Returns the file as bytes."""
     zz = api.zigzag_table()
     nc = len(sampling)
     if nc not in (1, 3) or len(qtables) != nc:
@@ -333,3 +333,83 @@ def _colorspace(comps, jfif, adobe):
     if adobe is not None:
         return "RGB" if adobe == 0 else "YCbCr"
     return "RGB" if [c["id"] for c in comps] == [ord("R"), ord("G"), ord("B")] else "YCbCr"
+
+
+# ------------------------------------------------------------------------------------------ progressive files (SOF2)
+def _segments(data):
+    """(marker, offset of the payload, its length) of the marker segments from SOI to EOI, entropy-coded data skipped, by read_jpeg's
+    walk; where read_jpeg would refuse the next segment the walk just ends"""
+    i, n = 2, len(data)
+    while i + 4 <= n and data[i] == 0xFF:
+        m = data[i + 1]
+        if m == 0xFF:
+            i += 1  # fill byte
+            continue
+        L = struct.unpack_from(">H", data, i + 2)[0]
+        if m in (0xD9, 0x01) or 0xD0 <= m <= 0xD7 or L < 2 or i + 2 + L > n:
+            return
+        yield m, i + 4, L - 2
+        i += 2 + L
+        if m == 0xDA:
+            try:
+                i = _entropy_end(data, i)
+            except JpegFormatError:
+                return
+
+
+def sof_marker(data):
+    """the marker code of the file's first frame header (SOFn: 0xC0 baseline, 0xC2 progressive, ...), found by walking the marker
+    segments; None if there is none or the file is malformed before it.  Never raises."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        return None
+    for m, _, _ in _segments(data):
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return m
+    return None
+
+
+def read_progressive_jpeg(data):
+    """Parse a progressive Huffman JPEG (SOF2) that uses spectral selection only (T.81 Annex G, Ah = Al = 0) and carries restart
+    markers in every scan: what write_progressive_jpeg writes.  Returns read_jpeg's dict with sof = 0xC2; every scan also carries
+    'ss', 'se', 'ah', 'al' (its band, zig-zag; ah = al = 0), and its 'huffman' and 'restart_interval' are those in force at it (such a
+    file redefines DHT and DRI from scan to scan).  A DC scan's components carry a 'ta' and an AC scan's a 'td' the scan does not use.
+
+    The rules for segments, frame header, DQT, DHT and the SOS header are read_jpeg's own: they are applied to a copy of the file whose
+    frame marker is rewritten to SOF1 and whose bands to 0..63, which changes no length and no offset.  On top of them this refuses
+    (JpegFormatError) a file that is not SOF2, successive approximation, a scan without restart markers, an interleaved AC scan, a band
+    that mixes DC and AC or is out of order, a position of a component coded a second time, and an AC scan of a component whose DC scan
+    has not come.  A band that no scan codes is legal: those coefficients are zero, as libjpeg decodes a truncated script."""
+    data = bytes(data)
+    sof = sof_marker(data)
+    if sof != 0xC2:
+        if sof is None:
+            read_jpeg(data, require_restart=False)  # malformed before any frame header: its message
+        raise JpegFormatError(f"not a progressive file: the frame header is SOF{(sof or 0xC0) - 0xC0}, not SOF2")
+    twin, bands = bytearray(data), []
+    for m, p, n in _segments(data):
+        if m == 0xC2:
+            twin[p - 3] = 0xC1
+        elif m == 0xDA and n and n == 4 + 2 * data[p]:  # (any other SOS is malformed: read_jpeg says so)
+            bands.append(tuple(data[p + n - 3:p + n]))
+            twin[p + n - 3:p + n] = bytes([0, 63, 0])
+    info = read_jpeg(bytes(twin), require_restart=False)
+    info["sof"] = 0xC2
+    coded = [set() for _ in info["components"]]
+    for k, (sc, (ss, se, a)) in enumerate(zip(info["scans"], bands)):
+        sc.update(ss=ss, se=se, ah=a >> 4, al=a & 15)
+        if a:
+            raise JpegFormatError(f"not supported: successive approximation (scan {k}: Ah {a >> 4}, Al {a & 15})")
+        if sc["restart_interval"] == 0:
+            raise JpegFormatError(f"not supported: a progressive scan without restart markers (scan {k}: no DRI or restart interval 0)")
+        if ss > se or se > 63 or (ss == 0 and se != 0):
+            raise JpegFormatError(f"malformed SOS: band {ss}..{se} (scan {k}; 0..0, or an AC band inside 1..63)")
+        if ss > 0 and len(sc["components"]) > 1:
+            raise JpegFormatError(f"malformed SOS: an interleaved AC scan (scan {k}: T.81 G.1.1.1.1)")
+        for c in sc["components"]:
+            if ss > 0 and 0 not in coded[c["index"]]:
+                raise JpegFormatError(f"malformed file: an AC scan of component {c['index']} before its DC scan (scan {k})")
+            if not coded[c["index"]].isdisjoint(range(ss, se + 1)):
+                raise JpegFormatError(f"malformed file: a position of component {c['index']} is coded a second time (scan {k}: band {ss}..{se})")
+            coded[c["index"]].update(range(ss, se + 1))
+    return info

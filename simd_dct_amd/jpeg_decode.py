@@ -1,9 +1,10 @@
-"""Baseline JPEG -> 8-bit planes on the GPU (libmdct_jpegdec.so, include/mdct_jpegdec.h; libmdct_jpegdec_unmarked.so,
-include/mdct_jpegdec_unmarked.h).
+"""Baseline and progressive (spectral selection) JPEG -> 8-bit planes on the GPU (libmdct_jpegdec.so, include/mdct_jpegdec.h;
+libmdct_jpegdec_unmarked.so, include/mdct_jpegdec_unmarked.h; libmdct_jpegdec_prog.so, include/mdct_jpegdec_prog.h).
 
-decode_jpeg parses the file on the host (jfif.read_jpeg), uploads each scan and decodes it into quantised int16 coefficient planes:
-a scan with restart markers by finding its restart intervals (mdct_jpegdec_index) and decoding them (mdct_jpegdec_decode), a scan
-without by mdct_jpegdec_decode_unmarked.  It checks every scan's status, and runs
+decode_jpeg parses the file on the host (read_file: jfif.read_jpeg, or jfif.read_progressive_jpeg for a SOF2 file), uploads each scan
+and decodes it into quantised int16 coefficient planes: a baseline scan with restart markers by finding its restart intervals
+(mdct_jpegdec_index) and decoding them (mdct_jpegdec_decode), one without by mdct_jpegdec_decode_unmarked, a scan of a progressive
+file by mdct_jpegdec_index and mdct_jpegdec_prog_decode into its band of the planes.  It checks every scan's status, and runs
 mdct_inv_i16_u8_batch over the planes with each component's DQT as the table.  One uint8 plane per component, cropped to the
 component's size (T.81 A.1.1).  With mode="RGB" the planes go through one more launch, mdct_jpegcolor_to_rgb
 (libmdct_jpegcolor.so, include/mdct_jpegcolor.h): chroma upsampling and YCbCr -> RGB as libjpeg-turbo's default decode gives them.
@@ -16,7 +17,7 @@ import ctypes
 
 import numpy as np
 
-from . import _jpegcolor_lib, _jpegdec_lib, _jpegdec_unmarked_lib, api, jfif
+from . import _jpegcolor_lib, _jpegdec_lib, _jpegdec_prog_lib, _jpegdec_unmarked_lib, api, jfif
 from .api import _ptr, _stream
 
 
@@ -28,6 +29,9 @@ class JpegDecodeError(RuntimeError):
         super().__init__(msg)
         self.scan = scan
         self.status = status
+
+
+STATUS_NAMES = _jpegdec_prog_lib.STATUS_NAMES  # every interval status a restart-marked or progressive scan can end in
 
 
 def last_error():
@@ -133,6 +137,35 @@ def decode_unmarked(desc, tables, scan, workspace, status, scan_len=None, sync_r
         raise api.MdctError(f"mdct_jpegdec status {rc}: {unmarked_last_error()}")
 
 
+def prog_last_error():
+    return _jpegdec_prog_lib.load().mdct_jpegdec_prog_last_error().decode()
+
+
+def prog_intervals(desc, ss, se):
+    """mdct_jpegdec_prog_intervals (host only): the scan's restart intervals; MdctError for a descriptor or band the library refuses"""
+    n = int(_jpegdec_prog_lib.load().mdct_jpegdec_prog_intervals(ctypes.byref(desc), ss, se))
+    if n == 0:
+        raise api.MdctError(f"invalid scan descriptor: {prog_last_error()}")
+    return n
+
+
+def decode_prog(desc, ss, se, tables, scan, offsets, status, scan_len=None, stream=None):
+    """mdct_jpegdec_prog_decode: one scan of a progressive file, band ss..se; offsets as index() leaves them"""
+    L = scan.numel() if scan_len is None else scan_len
+    rc = _jpegdec_prog_lib.load().mdct_jpegdec_prog_decode(ctypes.byref(desc), ss, se, tables.handle, _ptr(scan), L, _ptr(offsets), _ptr(status),
+                                                           _stream(stream))
+    if rc != 0:
+        raise api.MdctError(f"mdct_jpegdec_prog status {rc}: {prog_last_error()}")
+
+
+def read_file(data):
+    """the parser the file's frame header asks for: jfif.read_progressive_jpeg for SOF2, jfif.read_jpeg(require_restart=False) for
+    everything else (which refuses what it always refused)"""
+    if jfif.sof_marker(data) == 0xC2:
+        return jfif.read_progressive_jpeg(data)
+    return jfif.read_jpeg(data, require_restart=False)
+
+
 def _ceil(a, b):
     return -(-a // b)
 
@@ -159,12 +192,15 @@ def scan_plan(info, si, sc, geo, grid, coefs):
     """Everything decode_jpeg settles about scan si on the host before its first launch: the Huffman specifications the scan names
     (JpegFormatError for one that is not defined), their validation (tables_check) and the descriptor over the coefficient planes,
     which the library it goes to must accept (MdctError).  coefs: one int16 tensor per component, [rows, blocks_x * 8].
+    A scan of a progressive file (one with 'ss' / 'se') names only the tables of its band's class: DC for 0..0, AC for an AC band.
     -> (specs, desc)"""
     mcus_x, mcus_y, members = scan_geometry(info, sc, geo, grid)
     specs = [None] * 4
     planes = []
+    band = (sc["ss"], sc["se"]) if "ss" in sc else None
     for c, (ci, h, v) in zip(sc["components"], members):
-        for slot, key in ((c["td"], (0, c["td"])), (2 + c["ta"], (1, c["ta"]))):
+        dc, ac = (c["td"], (0, c["td"])), (2 + c["ta"], (1, c["ta"]))
+        for slot, key in (dc, ac) if band is None else (dc,) if band == (0, 0) else (ac,):
             if key not in sc["huffman"]:
                 raise jfif.JpegFormatError(f"scan {si} uses Huffman table {key} that is not defined")
             specs[slot] = sc["huffman"][key]
@@ -172,7 +208,9 @@ def scan_plan(info, si, sc, geo, grid, coefs):
     if tables_check(specs) != 0:
         raise api.MdctError(f"scan {si}: {last_error()}")
     desc = scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"])
-    if sc["restart_interval"]:
+    if band is not None:
+        prog_intervals(desc, *band)
+    elif sc["restart_interval"]:
         n_intervals(desc)
     elif unmarked_workspace(desc, sc["end"] - sc["start"]) == 0:
         raise api.MdctError(f"invalid scan descriptor: {unmarked_last_error()}")
@@ -283,20 +321,21 @@ def scaled_planes(info, coefs, scale_denom, stream=None, replicate=False):
 
 
 def decode_coefficients(data, device=None, stream=None, *, info=None):
-    """The front of decode_jpeg on its own: parse the file (jfif.read_jpeg), plan and entropy-decode every scan on the GPU.  No inverse
-    DCT runs.  -> (info, coefs): read_jpeg's dict and one quantised int16 coefficient plane per component on the device,
-    [blocks_y * 8, blocks_x * 8], padded to the MCU grid (geometry), not dequantised.  info: read_jpeg(data, require_restart=False) if
-    the caller has parsed the file already.  Raises as decode_jpeg does: jfif.JpegFormatError for a file outside the supported subset,
-    JpegDecodeError when a scan does not decode cleanly."""
+    """The front of decode_jpeg on its own: parse the file (read_file), plan and entropy-decode every scan on the GPU.  No inverse
+    DCT runs.  -> (info, coefs): the reader's dict and one quantised int16 coefficient plane per component on the device,
+    [blocks_y * 8, blocks_x * 8], padded to the MCU grid (geometry), not dequantised.  info: read_file(data) if the caller has parsed
+    the file already.  The scans of a progressive file each fill their band of the same planes; a band no scan codes stays zero.
+    Raises as decode_jpeg does: jfif.JpegFormatError for a file outside the supported subset, JpegDecodeError when a scan does not
+    decode cleanly."""
     import torch
 
     if info is None:
-        info = jfif.read_jpeg(data, require_restart=False)
+        info = read_file(data)
     dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
     raw = bytes(data)
     geo, grid = geometry(info)
     # zeroed: a non-interleaved scan of a subsampled component covers its own block grid (T.81 A.2.2), which may be smaller than the
-    # plane padded to the MCU grid
+    # plane padded to the MCU grid; and a progressive scan stores non-zero levels only, into a band that must be zero
     coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
     with torch.cuda.device(dev):
         for si, sc in enumerate(info["scans"]):
@@ -311,7 +350,9 @@ def decode_coefficients(data, device=None, stream=None, *, info=None):
 
 
 def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None, layout="HWC", scale_denom=1):
-    """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file).  Returns one uint8
+    """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file), or a progressive one
+    that uses spectral selection only and carries restart markers (jfif.read_progressive_jpeg: what encode_jpeg(progressive=True)
+    writes; successive approximation is refused).  Returns one uint8
     tensor [height, width] per component (cropped to its true size); with coefficients=True also the quantised int16 coefficient planes
     ([blocks_y * 8, blocks_x * 8], padded to the MCU grid): (planes, coefficient planes).
     mode="RGB" returns one uint8 image instead of the planes, [height, width, 3] (layout="HWC") or [3, height, width] (layout="CHW"),
@@ -330,7 +371,7 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
         raise ValueError(f"mode {mode!r} (None or 'RGB')")
     if layout not in _LAYOUTS:
         raise ValueError(f"layout {layout!r} ('HWC' or 'CHW')")
-    info = jfif.read_jpeg(data, require_restart=False)
+    info = read_file(data)
     if mode == "RGB":
         _colour_params(info)
     dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
@@ -402,8 +443,8 @@ def to_rgb(planes, sampling, width, height, colour="YCbCr", layout="HWC", out=No
 
 
 def decode_scan(torch, si, sc, desc, tables, seg, dev, stream=None):
-    """decode scan si of read_jpeg's list as scan_plan planned it (seg: its bytes on the device) into the planes its descriptor names,
-    by the route its restart interval asks for, and wait for its status: per interval (restart-marked), or [code, blocks decoded]
+    """decode scan si of the reader's list as scan_plan planned it (seg: its bytes on the device) into the planes its descriptor names,
+    by the route its kind and restart interval ask for, and wait for its status: per interval (restart-marked, progressive), or [code, blocks decoded]
     (no markers; a NOT_SYNCHRONISED result, an ordinary status and not a fault, is decoded once more with one fix round per chunk,
     which always converges).  Returns the status; JpegDecodeError for a scan that did not decode cleanly."""
     L = sc["end"] - sc["start"]
@@ -423,15 +464,19 @@ def decode_scan(torch, si, sc, desc, tables, seg, dev, stream=None):
             raise JpegDecodeError(f"scan {si} (no restart markers): {_jpegdec_unmarked_lib.STATUS_NAMES.get(int(st[0]), int(st[0]))} "
                                   f"after {int(st[1])} blocks", scan=si, status=st)
         return st
-    n = n_intervals(desc)
+    band = (sc["ss"], sc["se"]) if "ss" in sc else None
+    n = n_intervals(desc) if band is None else prog_intervals(desc, *band)
     off = torch.empty(n + 1, dtype=torch.int64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     index(seg, n, off, status, scan_len=L, stream=stream)
-    decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
+    if band is None:
+        decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
+    else:
+        decode_prog(desc, band[0], band[1], tables, seg, off, status, scan_len=L, stream=stream)
     st = status.cpu().numpy()
     bad = np.flatnonzero(st)
     if bad.size:
         k = int(bad[0])
-        raise JpegDecodeError(f"scan {si}: {bad.size} of {n} restart intervals failed; interval {k}: "
-                              f"{_jpegdec_lib.STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
+        raise JpegDecodeError(f"scan {si}{'' if band is None else f' (band {band[0]}..{band[1]})'}: {bad.size} of {n} restart intervals failed; "
+                              f"interval {k}: {STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
     return st

@@ -362,8 +362,7 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     progressive=True) writes with its default bands.  The planes are padded to the MCU grid, mdct_fwd_u8_i16
     with the level shift and the quality tables makes the quantised coefficients the pixel coders are defined on, and the band coders
     saturate AC levels to +-1023 as the pixel coders do.  The tables are always made for the image: optimize=False is accepted and
-    plays no part, nor does two_launch; interleaved selects the form of the DC scan.  The engine's own decoder does not read the
-    file."""
+    plays no part, nor does two_launch; interleaved selects the form of the DC scan.  decode_jpeg reads the file back."""
     import torch
 
     q = _quality(quality)

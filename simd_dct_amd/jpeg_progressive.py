@@ -3,8 +3,8 @@ planes -> a SOF2 file with spectral selection (T.81 Annex G, Ah = Al = 0): one D
 end-of-band runs, every scan with a restart interval per row and a Huffman table made for it.
 
 prog_dc_histogram, prog_dc_rows, prog_ac_histogram and prog_ac_rows are thin wrappers of the C-ABI on device tensors; encode is what
-jpeg_transcode.encode_coefficients(progressive=True) runs.  Successive approximation is out of scope, and so is reading these files:
-jfif.read_jpeg refuses SOF2.  torch is used for device memory and streams only.
+jpeg_transcode.encode_coefficients(progressive=True) runs.  Successive approximation is out of scope.  jpeg_decode reads these files back
+(jfif.read_progressive_jpeg, libmdct_jpegdec_prog.so).  torch is used for device memory and streams only.
 """
 import numpy as np
 

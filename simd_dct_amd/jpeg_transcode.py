@@ -156,8 +156,8 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
     selects the form of the DC scan only: True one interleaved DC scan (the samplings above), False one per component.  bands: per
     component a list of (ss, se) that tiles 1..63 in order (default: luma (1, 2), (3, 9), (10, 63), chroma (1, 63); grey as luma; anything
     else is a ValueError); without progressive it must be None.  All statistics launches run first and one copy brings every histogram
-    and the loss count back; then all coding and packing launches, and one copy of the lengths.  The engine's own decoder does not
-    read these files (jfif.read_jpeg refuses SOF2)."""
+    and the loss count back; then all coding and packing launches, and one copy of the lengths.  jpeg_decode reads these files back
+    (jfif.read_progressive_jpeg, libmdct_jpegdec_prog.so)."""
     import torch
 
     _bools(optimize, interleaved)
@@ -278,8 +278,8 @@ def plan_transform(width, height, sampling, transform, trim):
 
 
 def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleaved=False, progressive=False, device=None, stream=None):
-    """Rewrite a baseline JPEG without touching its coefficients (jpegtran): decode_coefficients, the optional transform,
-    encode_coefficients.  Returns the new file as bytes.
+    """Rewrite a baseline JPEG, or a progressive one decode_jpeg reads, without touching its coefficients (jpegtran):
+    decode_coefficients, the optional transform, encode_coefficients.  Returns the new file as bytes.
 
     transform: None or 'flip_h', 'flip_v', 'transpose', 'transverse', 'rot90' (clockwise), 'rot180', 'rot270'.  A transposing operation
     swaps width and height and each component's (h, v), and transposes every quantisation table.  A source axis the operation mirrors
@@ -290,7 +290,7 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     MCU row (three components with 4:4:4, 4:2:2 or 4:2:0 AFTER the transform: ValueError otherwise, before any device work).  Either way
     the output goes through the per-interval decoder ever after, whatever the input's scan form and restart interval were.
     progressive=True: the output is a progressive file with spectral selection (encode_coefficients: optimize must be True; interleaved
-    selects the form of its DC scan); the engine's own decoder does not read it back.
+    selects the form of its DC scan).
     The quantisation tables (one per component, equal ones shared) and the colour space (grey, YCbCr, Adobe RGB) survive.
     Blocks of the padded planes beyond a component's own grid are zero after a non-interleaved input; an interleaved output codes them
     as they are -- they are invisible, which is not a loss.
@@ -299,8 +299,8 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     api.MdctError if a coefficient cannot be written in a baseline scan (a DC difference beyond +-2047 can arise where blocks become
     neighbours that were not).
 
-    Out of scope: copying EXIF, ICC or comment segments (APPn and COM are dropped but for the colour-space markers); progressive or
-    arithmetic-coded INPUT (read_jpeg refuses both); progressive output with successive approximation; jpegtran's default of leaving an unmirrored edge strip in place (here: perfect,
+    Out of scope: copying EXIF, ICC or comment segments (APPn and COM are dropped but for the colour-space markers); arithmetic-coded
+    INPUT; successive approximation, in or out; jpegtran's default of leaving an unmirrored edge strip in place (here: perfect,
     trim, or an error); re-quantising (changing quality)."""
     import torch
 
@@ -311,7 +311,7 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
         raise ValueError("progressive=True needs optimize=True: the Annex K tables have no codes for end-of-band runs")
     if transform is not None and transform not in MIRRORED:
         raise ValueError(f"transform {transform!r} (None or one of {', '.join(TRANSFORMS)})")
-    info = jfif.read_jpeg(data, require_restart=False)
+    info = jpeg_decode.read_file(data)
     comps = info["components"]
     sampling = [(c["h"], c["v"]) for c in comps]
     (sw, sh), (ow, oh), osampling = plan_transform(info["width"], info["height"], sampling, transform, trim)
