@@ -68,6 +68,24 @@ def _stream(stream=None):
     return None
 
 
+def _on_stream(stream=None, device=None):
+    """The torch stream context the body of a call that takes `stream=` runs under, so that everything torch enqueues for it --
+    allocations (the caching allocator ties a block to the stream current when it is handed out), fills, uploads and the copies the host
+    reads -- is ordered on the stream its kernels are launched on (_stream).  None: a null context, torch's current stream is that
+    stream already.  A torch.cuda.Stream: torch.cuda.stream(stream).  A raw hipStream_t (an integer): torch.cuda.ExternalStream on
+    `device` (default: the current device); the handle 0 is the device's default stream."""
+    import contextlib
+
+    if stream is None:
+        return contextlib.nullcontext()
+    import torch
+
+    if not isinstance(stream, torch.cuda.Stream):
+        handle = int(getattr(stream, "cuda_stream", stream))
+        stream = torch.cuda.default_stream(device) if handle == 0 else torch.cuda.ExternalStream(handle, device=device)
+    return torch.cuda.stream(stream)
+
+
 def init(device=0):
     """mdct_init: replaces _DetectCPUFeatures() (simd_platform.c:68)."""
     _check(_lib.load().mdct_init(int(device)))

@@ -310,13 +310,14 @@ def scaled_planes(info, coefs, scale_denom, stream=None, replicate=False):
     sgeo, (sw, sh) = scaled_geometry(info, scale_denom)
     reps = colour_sampling(info, scale_denom)[1] if replicate else [(1, 1)] * len(sgeo)
     luts = component_luts(info)
-    px = [torch.empty((g[3] * sg[0] * r[1], g[2] * sg[0] * r[0]), dtype=torch.uint8, device=q.device) for g, sg, q, r in zip(geo, sgeo, coefs, reps)]
-    full = [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, sg, lut in zip(px, coefs, geo, sgeo, luts) if sg[0] == 8]
-    small = [(p, q, g[2], g[3], lut, sg[0], r) for p, q, g, sg, lut, r in zip(px, coefs, geo, sgeo, luts, reps) if sg[0] != 8]
-    if full:
-        api.u8_i16_batch("inv", full, level_shift=True, stream=stream)
-    if small:
-        scaled_inverse(small, level_shift=True, stream=stream)
+    with api._on_stream(stream, coefs[0].device):
+        px = [torch.empty((g[3] * sg[0] * r[1], g[2] * sg[0] * r[0]), dtype=torch.uint8, device=q.device) for g, sg, q, r in zip(geo, sgeo, coefs, reps)]
+        full = [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, sg, lut in zip(px, coefs, geo, sgeo, luts) if sg[0] == 8]
+        small = [(p, q, g[2], g[3], lut, sg[0], r) for p, q, g, sg, lut, r in zip(px, coefs, geo, sgeo, luts, reps) if sg[0] != 8]
+        if full:
+            api.u8_i16_batch("inv", full, level_shift=True, stream=stream)
+        if small:
+            scaled_inverse(small, level_shift=True, stream=stream)
     return [p[:sg[2], :sg[1]] if r == (1, 1) else p[:sh, :sw] for p, sg, r in zip(px, sgeo, reps)]
 
 
@@ -336,8 +337,8 @@ def decode_coefficients(data, device=None, stream=None, *, info=None):
     geo, grid = geometry(info)
     # zeroed: a non-interleaved scan of a subsampled component covers its own block grid (T.81 A.2.2), which may be smaller than the
     # plane padded to the MCU grid; and a progressive scan stores non-zero levels only, into a band that must be zero
-    coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), api._on_stream(stream, dev):
+        coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
         for si, sc in enumerate(info["scans"]):
             specs, desc = scan_plan(info, si, sc, geo, grid, coefs)
             tables = Tables(specs)
@@ -362,6 +363,10 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
     IDCT, and a subsampled component keeps more of its own samples before any upsampling (at 1/8 what upsampling is left is plain
     replication, as libjpeg-turbo does it: colour_sampling).  The coefficient planes stay the full ones.
     The entropy decode, which is most of a decode's time, is the same at every scale: the scaled picture saves memory, not much time.
+    stream: None (torch's current stream), a torch.cuda.Stream or a raw hipStream_t.  All device work of the call -- its kernels, its own
+    allocations, fills and uploads, and the copies of the scans' statuses that the host waits for -- is ordered on that stream
+    (api._on_stream), whatever torch's current stream is.  The returned device tensors are ready on `stream`, not necessarily on the
+    caller's current stream: a consumer on another stream waits for `stream` first (wait_stream / an event).
     Raises jfif.JpegFormatError for a file outside the supported subset and JpegDecodeError when a scan does not decode cleanly."""
     import torch
 
@@ -377,7 +382,7 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
     dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
     geo, _ = geometry(info)
     _, coefs = decode_coefficients(data, dev, stream, info=info)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), api._on_stream(stream, dev):
         if scale_denom != 1:
             out = scaled_planes(info, coefs, scale_denom, stream=stream, replicate=mode == "RGB")
             if mode == "RGB":
@@ -431,7 +436,8 @@ def to_rgb(planes, sampling, width, height, colour="YCbCr", layout="HWC", out=No
         arr[k] = _jpegcolor_lib.Plane(p.data_ptr(), p.stride(0), p.shape[1], p.shape[0], h, v)
     shape = (height, width, 3) if layout == "HWC" else (3, height, width)
     if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=planes[0].device)
+        with api._on_stream(stream, planes[0].device):
+            out = torch.empty(shape, dtype=torch.uint8, device=planes[0].device)
     if out.dtype != torch.uint8 or tuple(out.shape) != shape or out.stride(-1) != 1 or (layout == "HWC" and out.stride(1) != 3):
         raise ValueError(f"out: uint8 {list(shape)} with contiguous {'pixels' if layout == 'HWC' else 'rows'}")
     pitch, stride = (out.stride(0), 0) if layout == "HWC" else (out.stride(1), out.stride(0))
@@ -444,39 +450,40 @@ def to_rgb(planes, sampling, width, height, colour="YCbCr", layout="HWC", out=No
 
 def decode_scan(torch, si, sc, desc, tables, seg, dev, stream=None):
     """decode scan si of the reader's list as scan_plan planned it (seg: its bytes on the device) into the planes its descriptor names,
-    by the route its kind and restart interval ask for, and wait for its status: per interval (restart-marked, progressive), or [code, blocks decoded]
+    by the route its kind and restart interval ask for, and wait for its status (the copy is ordered on the scan's stream, api._on_stream): per interval (restart-marked, progressive), or [code, blocks decoded]
     (no markers; a NOT_SYNCHRONISED result, an ordinary status and not a fault, is decoded once more with one fix round per chunk,
     which always converges).  Returns the status; JpegDecodeError for a scan that did not decode cleanly."""
-    L = sc["end"] - sc["start"]
-    if sc["restart_interval"] == 0:
-        nbytes = unmarked_workspace(desc, L)
-        if nbytes == 0:
-            raise api.MdctError(f"invalid scan descriptor: {unmarked_last_error()}")
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # the caching allocator's blocks are 512-byte aligned
-        status = torch.empty(2, dtype=torch.int32, device=dev)
-        decode_unmarked(desc, tables, seg, work, status, scan_len=L, stream=stream)
-        st = status.cpu().numpy()
-        if st[0] == _jpegdec_unmarked_lib.NOT_SYNCHRONISED:
-            rounds = max(1, _ceil(L, _jpegdec_unmarked_lib.CHUNK_BYTES))
-            decode_unmarked(desc, tables, seg, work, status, scan_len=L, sync_rounds=rounds, stream=stream)
+    with api._on_stream(stream, dev):
+        L = sc["end"] - sc["start"]
+        if sc["restart_interval"] == 0:
+            nbytes = unmarked_workspace(desc, L)
+            if nbytes == 0:
+                raise api.MdctError(f"invalid scan descriptor: {unmarked_last_error()}")
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # the caching allocator's blocks are 512-byte aligned
+            status = torch.empty(2, dtype=torch.int32, device=dev)
+            decode_unmarked(desc, tables, seg, work, status, scan_len=L, stream=stream)
             st = status.cpu().numpy()
-        if st[0] != 0:
-            raise JpegDecodeError(f"scan {si} (no restart markers): {_jpegdec_unmarked_lib.STATUS_NAMES.get(int(st[0]), int(st[0]))} "
-                                  f"after {int(st[1])} blocks", scan=si, status=st)
+            if st[0] == _jpegdec_unmarked_lib.NOT_SYNCHRONISED:
+                rounds = max(1, _ceil(L, _jpegdec_unmarked_lib.CHUNK_BYTES))
+                decode_unmarked(desc, tables, seg, work, status, scan_len=L, sync_rounds=rounds, stream=stream)
+                st = status.cpu().numpy()
+            if st[0] != 0:
+                raise JpegDecodeError(f"scan {si} (no restart markers): {_jpegdec_unmarked_lib.STATUS_NAMES.get(int(st[0]), int(st[0]))} "
+                                      f"after {int(st[1])} blocks", scan=si, status=st)
+            return st
+        band = (sc["ss"], sc["se"]) if "ss" in sc else None
+        n = n_intervals(desc) if band is None else prog_intervals(desc, *band)
+        off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        index(seg, n, off, status, scan_len=L, stream=stream)
+        if band is None:
+            decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
+        else:
+            decode_prog(desc, band[0], band[1], tables, seg, off, status, scan_len=L, stream=stream)
+        st = status.cpu().numpy()
+        bad = np.flatnonzero(st)
+        if bad.size:
+            k = int(bad[0])
+            raise JpegDecodeError(f"scan {si}{'' if band is None else f' (band {band[0]}..{band[1]})'}: {bad.size} of {n} restart intervals failed; "
+                                  f"interval {k}: {STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
         return st
-    band = (sc["ss"], sc["se"]) if "ss" in sc else None
-    n = n_intervals(desc) if band is None else prog_intervals(desc, *band)
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    index(seg, n, off, status, scan_len=L, stream=stream)
-    if band is None:
-        decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
-    else:
-        decode_prog(desc, band[0], band[1], tables, seg, off, status, scan_len=L, stream=stream)
-    st = status.cpu().numpy()
-    bad = np.flatnonzero(st)
-    if bad.size:
-        k = int(bad[0])
-        raise JpegDecodeError(f"scan {si}{'' if band is None else f' (band {band[0]}..{band[1]})'}: {bad.size} of {n} restart intervals failed; "
-                              f"interval {k}: {STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
-    return st

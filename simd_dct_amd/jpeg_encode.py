@@ -118,7 +118,8 @@ def to_planes(image, subsampling="4:2:0", layout="HWC", planes=None, stream=None
     if not ok:
         raise ValueError("image: contiguous innermost dimension (HWC: 3 contiguous bytes per pixel)")
     if planes is None:
-        planes = [torch.empty((ph, pw), dtype=torch.uint8, device=image.device) for _, _, pw, ph in sizes]
+        with api._on_stream(stream, image.device):
+            planes = [torch.empty((ph, pw), dtype=torch.uint8, device=image.device) for _, _, pw, ph in sizes]
     if len(planes) != len(sampling):
         raise ValueError(f"{len(planes)} planes for {len(sampling)} components")
     arr = (_jpegenc_lib.Plane * len(planes))()
@@ -185,7 +186,8 @@ def symbol_histogram(planes, sampling, luts, interleaved=False, hist=None, strea
     arr = _plane_array(planes, sampling)
     tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
     if hist is None:
-        hist = torch.empty((2, _jpegenc_opt_lib.HIST_CLASS), dtype=torch.int32, device=planes[0].device)
+        with api._on_stream(stream, planes[0].device):
+            hist = torch.empty((2, _jpegenc_opt_lib.HIST_CLASS), dtype=torch.int32, device=planes[0].device)
     if hist.dtype != torch.int32 or tuple(hist.shape) != (2, _jpegenc_opt_lib.HIST_CLASS) or not hist.is_contiguous():
         raise ValueError("hist: a contiguous int32 tensor [2, 272]")
     rc = _jpegenc_opt_lib.load().mdct_jpegenc_opt_stats(arr, len(planes), tabs[0].ctypes.data, tabs[-1].ctypes.data, int(interleaved), hist.data_ptr(), _stream(stream))
@@ -208,7 +210,8 @@ def optimal_table(counts):
 
 
 def optimal_tables(hist, grey=False):
-    """hist of symbol_histogram (a device tensor is copied to the host: that waits for the stream) -> {which: (bits16, vals)} keyed like
+    """hist of symbol_histogram (a device tensor is copied to the host on torch's current stream: that waits for the histogram only when
+    it was made on that stream, as it is inside encode_jpeg, which runs under api._on_stream) -> {which: (bits16, vals)} keyed like
     api.huffman_spec: 0 DC luminance, 1 AC luminance, 2 DC chrominance, 3 AC chrominance (grey: 0 and 1 only)"""
     h = np.asarray(hist.cpu() if hasattr(hist, "cpu") else hist).astype(np.int64).reshape(2, _jpegenc_opt_lib.HIST_CLASS) & 0xFFFFFFFF
     out = {}
@@ -281,29 +284,30 @@ def _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, tabs,
     """the colour image as one interleaved scan: front launch into planes on the MCU grid, scan_rows, the packing launch, one read-back.
     optimize: the statistics launch and the wait for its histogram first, then opt_scan_rows with the tables made from it"""
     dev = image.device
-    mcus_x, mcus_y, sizes = mcu_grid(W, H, sampling)
-    planes = to_planes(image, subsampling, layout, planes=[torch.empty((ph, pw), dtype=torch.uint8, device=dev) for pw, ph in sizes], stream=stream)
-    stride = opt_seg_stride(mcus_x * sum(h * v for h, v in sampling)) if optimize else scan_seg_stride(mcus_x, sampling)
-    seg = torch.empty((mcus_y * stride,), dtype=torch.uint8, device=dev)
-    counts = torch.empty((2, mcus_y), dtype=torch.int32, device=dev)
-    off = torch.empty((mcus_y + 1,), dtype=torch.int64, device=dev)
-    specs = None
-    if optimize:
-        specs = optimal_tables(symbol_histogram(planes, sampling, tabs, interleaved=True, stream=stream))  # the copy that waits for the histogram
-        uncoded = torch.zeros((1,), dtype=torch.int32, device=dev)
-        opt_scan_rows(planes, sampling, tabs, specs, seg, counts[0], counts[1], uncoded, seg_stride=stride, stream=stream)
-    else:
-        scan_rows(planes, sampling, (tabs[0], tabs[1]), seg, counts[0], counts[1], seg_stride=stride, stream=stream)
-    out = torch.empty((_first_capacity(sum(pw * ph for pw, ph in sizes)),), dtype=torch.uint8, device=dev)
-    api.jpeg_pack_rows(seg, counts[0], stride, mcus_y, out, off, ff_counts=counts[1], stream=stream)
-    end = int(off[-1].item())  # the one copy that waits for the scan
-    if end > out.numel():  # the segments are there: only the packing runs again, into the worst case
-        out = torch.empty((2 * mcus_y * stride,), dtype=torch.uint8, device=dev)
+    with api._on_stream(stream, dev):  # the allocations, the fill of `uncoded` and the copies the host reads: all on the stream of the launches
+        mcus_x, mcus_y, sizes = mcu_grid(W, H, sampling)
+        planes = to_planes(image, subsampling, layout, planes=[torch.empty((ph, pw), dtype=torch.uint8, device=dev) for pw, ph in sizes], stream=stream)
+        stride = opt_seg_stride(mcus_x * sum(h * v for h, v in sampling)) if optimize else scan_seg_stride(mcus_x, sampling)
+        seg = torch.empty((mcus_y * stride,), dtype=torch.uint8, device=dev)
+        counts = torch.empty((2, mcus_y), dtype=torch.int32, device=dev)
+        off = torch.empty((mcus_y + 1,), dtype=torch.int64, device=dev)
+        specs = None
+        if optimize:
+            specs = optimal_tables(symbol_histogram(planes, sampling, tabs, interleaved=True, stream=stream))  # the copy, on the call's stream, that waits for the histogram
+            uncoded = torch.zeros((1,), dtype=torch.int32, device=dev)
+            opt_scan_rows(planes, sampling, tabs, specs, seg, counts[0], counts[1], uncoded, seg_stride=stride, stream=stream)
+        else:
+            scan_rows(planes, sampling, (tabs[0], tabs[1]), seg, counts[0], counts[1], seg_stride=stride, stream=stream)
+        out = torch.empty((_first_capacity(sum(pw * ph for pw, ph in sizes)),), dtype=torch.uint8, device=dev)
         api.jpeg_pack_rows(seg, counts[0], stride, mcus_y, out, off, ff_counts=counts[1], stream=stream)
-        end = int(off[-1].item())
-    if optimize and int(uncoded.item()) != 0:
-        raise api.MdctError(f"{int(uncoded.item())} symbols of the scan have no code in the tables made for it")
-    return dict(scan=out[:end].cpu().numpy(), mcus_per_row=mcus_x), specs
+        end = int(off[-1].item())  # the one copy that waits for the scan: it is ordered on the call's stream
+        if end > out.numel():  # the segments are there: only the packing runs again, into the worst case
+            out = torch.empty((2 * mcus_y * stride,), dtype=torch.uint8, device=dev)
+            api.jpeg_pack_rows(seg, counts[0], stride, mcus_y, out, off, ff_counts=counts[1], stream=stream)
+            end = int(off[-1].item())
+        if optimize and int(uncoded.item()) != 0:
+            raise api.MdctError(f"{int(uncoded.item())} symbols of the scan have no code in the tables made for it")
+        return dict(scan=out[:end].cpu().numpy(), mcus_per_row=mcus_x), specs
 
 
 class _Scan:
@@ -362,7 +366,13 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     progressive=True) writes with its default bands.  The planes are padded to the MCU grid, mdct_fwd_u8_i16
     with the level shift and the quality tables makes the quantised coefficients the pixel coders are defined on, and the band coders
     saturate AC levels to +-1023 as the pixel coders do.  The tables are always made for the image: optimize=False is accepted and
-    plays no part, nor does two_launch; interleaved selects the form of the DC scan.  decode_jpeg reads the file back."""
+    plays no part, nor does two_launch; interleaved selects the form of the DC scan.  decode_jpeg reads the file back.
+
+    stream: None (torch's current stream), a torch.cuda.Stream or a raw hipStream_t.  All device work of the call -- its kernels, its own
+    allocations, fills and the upload of a host image, and the copies of the histogram, the scans' lengths and their bytes that the host
+    waits for -- is ordered on that stream (api._on_stream), whatever torch's current stream is.  A device image must be ready for
+    `stream`: work that produces it on another stream has to be waited for first (wait_stream / an event).  The bytes returned are
+    complete."""
     import torch
 
     q = _quality(quality)
@@ -385,9 +395,10 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     if isinstance(image, np.ndarray):
         image = torch.from_numpy(np.ascontiguousarray(image))
     if not image.is_cuda:
-        image = image.to(dev)
+        with api._on_stream(stream, dev):
+            image = image.to(dev)
     dev = image.device
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), api._on_stream(stream, dev):
         if progressive:
             from . import jpeg_progressive
 
@@ -408,13 +419,13 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
         tabs = [luma] + [chroma] * (len(planes) - 1)
         specs = uncoded = None
         if optimize:
-            specs = optimal_tables(symbol_histogram(planes, sampling, (luma, chroma), stream=stream), grey=grey)  # the copy that waits for the histogram
+            specs = optimal_tables(symbol_histogram(planes, sampling, (luma, chroma), stream=stream), grey=grey)  # the copy, on the call's stream, that waits for the histogram
             uncoded = torch.zeros((1,), dtype=torch.int32, device=dev)
         # ~0.2 bytes per pixel in practice; a scan that does not fit is coded again into its worst case
         scans = [_Scan(torch, dev, pw, ph, _first_capacity(pw * ph), optimize) for _, _, pw, ph in sizes]
         for k, (p, (_, _, pw, ph), sc) in enumerate(zip(planes, sizes, scans)):
             _run_scan(p, pw, ph, tabs[k], k > 0, sc, two_launch, stream, specs, uncoded)
-        ends = torch.stack([sc.off[-1] for sc in scans]).cpu().tolist()  # the one copy that waits for the scans
+        ends = torch.stack([sc.off[-1] for sc in scans]).cpu().tolist()  # the one copy that waits for the scans: it is ordered on the call's stream
         for k, (p, (_, _, pw, ph), sc) in enumerate(zip(planes, sizes, scans)):
             if ends[k] < 0:  # UINT64_MAX read as int64
                 raise api.MdctError(f"scan {k}: the one-launch coder reported a failure (row_offsets = UINT64_MAX)")

@@ -67,9 +67,10 @@ def prog_dc_histogram(planes, sampling, interleaved=False, cls=0, grids=None, hi
     if not isinstance(interleaved, (bool, np.bool_)):
         raise ValueError(f"interleaved {interleaved!r}: a bool")
     arr = _plane_array(planes, sampling, grids)
-    hist = _hist(torch, hist, (2, HIST_CLASS), planes[0])
-    if unrepresentable is None:
-        unrepresentable = torch.zeros((1,), dtype=torch.int32, device=planes[0].device)
+    with api._on_stream(stream, planes[0].device):  # the fill of a word made here is ordered in front of the launch that adds to it
+        hist = _hist(torch, hist, (2, HIST_CLASS), planes[0])
+        if unrepresentable is None:
+            unrepresentable = torch.zeros((1,), dtype=torch.int32, device=planes[0].device)
     rc = _jpegprog_lib.load().mdct_jpegprog_dc_stats(arr, len(planes), int(interleaved), cls, hist.data_ptr(), unrepresentable.data_ptr(), _stream(stream))
     if check and rc != 0:
         raise _error(rc)
@@ -101,9 +102,10 @@ def prog_ac_histogram(plane, ss, se, grid=None, hist=None, unrepresentable=None,
     import torch
 
     p = _plane(plane, *(grid or (None, None)))
-    hist = _hist(torch, hist, (AC_HIST,), plane)
-    if unrepresentable is None:
-        unrepresentable = torch.zeros((1,), dtype=torch.int32, device=plane.device)
+    with api._on_stream(stream, plane.device):
+        hist = _hist(torch, hist, (AC_HIST,), plane)
+        if unrepresentable is None:
+            unrepresentable = torch.zeros((1,), dtype=torch.int32, device=plane.device)
     rc = _jpegprog_lib.load().mdct_jpegprog_ac_stats(p, ss, se, hist.data_ptr(), unrepresentable.data_ptr(), _stream(stream))
     if check and rc != 0:
         raise _error(rc)
@@ -139,7 +141,7 @@ def encode(torch, coefs, tabs, width, height, sampling, mcus_x, mcus_y, colorspa
     n_dc = len(scans)
     scans += [([coefs[c]], [sampling[c]], [grids[c]], [c], ss, se, grids[c][1], grids[c][0]) for c in range(nc) for ss, se in bands[c]]
     n_ac = len(scans) - n_dc
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), api._on_stream(stream, dev):
         # one int32 block: the DC histograms, the AC histograms, then the words the kernels add to
         words = torch.zeros((n_dc * 2 * HIST_CLASS + n_ac * AC_HIST + 2,), dtype=torch.int32, device=dev)
         unrep, uncoded = words[-2:-1], words[-1:]
@@ -150,7 +152,7 @@ def encode(torch, coefs, tabs, width, height, sampling, mcus_x, mcus_y, colorspa
                 prog_dc_histogram(planes, samp, interleaved=len(planes) == 3, cls=min(comps[0], 1), grids=g, hist=dc_h[k], unrepresentable=unrep, stream=stream)
             else:
                 prog_ac_histogram(planes[0], ss, se, grid=g[0], hist=ac_h[k - n_dc], unrepresentable=unrep, stream=stream)
-        w = words.cpu().numpy().astype(np.int64) & 0xFFFFFFFF  # the copy that waits for the histograms brings the loss count with it
+        w = words.cpu().numpy().astype(np.int64) & 0xFFFFFFFF  # the copy, on the call's stream, that waits for the histograms brings the loss count with it
         if w[-2] != 0 and not saturate:
             raise api.MdctError(f"{int(w[-2])} coefficients cannot be written in a progressive scan (AC outside +-1023 or DC difference outside +-2047)")
         dc_counts = w[:n_dc * 2 * HIST_CLASS].reshape(n_dc, 2, HIST_CLASS).sum(axis=0)
@@ -170,7 +172,7 @@ def encode(torch, coefs, tabs, width, height, sampling, mcus_x, mcus_y, colorspa
                 prog_ac_rows(planes[0], ss, se, ac_specs[k - n_dc], segs[k], counts[k][0], counts[k][1], uncoded, unrep, grid=g[0], seg_stride=strides[k], stream=stream)
                 tables.append({(1, min(comps[0], 1)): ac_specs[k - n_dc]})
             packed.append(_pack(torch, segs[k], counts[k], strides[k], rows, rows * per * (4 if se == 0 else 64), dev, stream))
-        tail = torch.cat([off[-1:] for _, off in packed] + [words[-2:].to(torch.int64)]).cpu().tolist()  # the one copy that waits for the scans
+        tail = torch.cat([off[-1:] for _, off in packed] + [words[-2:].to(torch.int64)]).cpu().tolist()  # the one copy that waits for the scans: it is ordered on the call's stream
         ends, lost, nocode = tail[:-2], tail[-2], tail[-1]
         if lost and not saturate:
             raise api.MdctError(f"{lost} coefficients cannot be written in a progressive scan (AC outside +-1023 or DC difference outside +-2047)")

@@ -59,12 +59,13 @@ def coef_histogram(planes, sampling, interleaved=False, grids=None, hist=None, u
     if not isinstance(interleaved, (bool, np.bool_)):
         raise ValueError(f"interleaved {interleaved!r}: a bool")
     arr = _plane_array(planes, sampling, grids)
-    if hist is None:
-        hist = torch.empty((2, _jpegcoef_lib.HIST_CLASS), dtype=torch.int32, device=planes[0].device)
+    with api._on_stream(stream, planes[0].device):  # the fill of a word made here is ordered in front of the launch that adds to it
+        if hist is None:
+            hist = torch.empty((2, _jpegcoef_lib.HIST_CLASS), dtype=torch.int32, device=planes[0].device)
+        if unrepresentable is None:
+            unrepresentable = torch.zeros((1,), dtype=torch.int32, device=planes[0].device)
     if hist.dtype != torch.int32 or tuple(hist.shape) != (2, _jpegcoef_lib.HIST_CLASS) or not hist.is_contiguous():
         raise ValueError("hist: a contiguous int32 tensor [2, 272]")
-    if unrepresentable is None:
-        unrepresentable = torch.zeros((1,), dtype=torch.int32, device=planes[0].device)
     rc = _jpegcoef_lib.load().mdct_jpegcoef_stats(arr, len(planes), int(interleaved), hist.data_ptr(), unrepresentable.data_ptr(), _stream(stream))
     if check and rc != 0:
         raise _error(rc)
@@ -128,8 +129,9 @@ def _check_interleaved(sampling):
 
 def _pack(torch, seg, counts, stride, rows, pixels, dev, stream):
     """the packing launch into the small first buffer -> (out, off); the caller reads off[-1] and packs again if it did not fit"""
-    out = torch.empty((_first_capacity(pixels),), dtype=torch.uint8, device=dev)
-    off = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
+    with api._on_stream(stream, dev):
+        out = torch.empty((_first_capacity(pixels),), dtype=torch.uint8, device=dev)
+        off = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
     api.jpeg_pack_rows(seg, counts[0], stride, rows, out, off, ff_counts=counts[1], stream=stream)
     return out, off
 
@@ -201,7 +203,7 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
         return jpeg_progressive.encode(torch, coefs, tabs, width, height, sampling, mcus_x, mcus_y, colorspace, bool(interleaved), bands, stream)
     grey = nc == 1
     dev = coefs[0].device
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), api._on_stream(stream, dev):
         if interleaved:
             grids = None
             rows = [mcus_y]
@@ -215,7 +217,7 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
         hist, unrep, uncoded = words[:-2].view(2, _jpegcoef_lib.HIST_CLASS), words[-2:-1], words[-1:]
         if optimize:
             coef_histogram(coefs, sampling, interleaved=bool(interleaved), grids=grids, hist=hist, unrepresentable=unrep, stream=stream)
-            w = words.cpu()  # the copy that waits for the histogram brings the loss count with it
+            w = words.cpu()  # the copy, on the call's stream, that waits for the histogram brings the loss count with it
             if int(w[-2]) != 0:
                 raise api.MdctError(f"{int(w[-2])} coefficients cannot be written in a baseline scan (AC outside +-1023 or DC difference outside +-2047)")
             specs = optimal_tables(w[:-2].view(2, _jpegcoef_lib.HIST_CLASS), grey=grey)
@@ -232,7 +234,7 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
                 coef_rows(p, sp, segs[k], counts[k][0], counts[k][1], uncoded, unrep, grid=grids[k], seg_stride=strides[k], stream=stream)
             pixels = [bx * by * 64 for bx, by in grids]
         packed = [_pack(torch, s, c, st, r, px, dev, stream) for s, c, st, r, px in zip(segs, counts, strides, rows, pixels)]
-        tail = torch.cat([off[-1:] for _, off in packed] + [words[-2:].to(torch.int64)]).cpu().tolist()  # the one copy that waits for the scans
+        tail = torch.cat([off[-1:] for _, off in packed] + [words[-2:].to(torch.int64)]).cpu().tolist()  # the one copy that waits for the scans: it is ordered on the call's stream
         ends, lost, nocode = tail[:-2], tail[-2], tail[-1]
         if lost:
             raise api.MdctError(f"{lost} coefficients cannot be written in a baseline scan (AC outside +-1023 or DC difference outside +-2047)")
@@ -295,6 +297,11 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     Blocks of the padded planes beyond a component's own grid are zero after a non-interleaved input; an interleaved output codes them
     as they are -- they are invisible, which is not a loss.
 
+    stream: None (torch's current stream), a torch.cuda.Stream or a raw hipStream_t.  All device work of the call -- the kernels of the
+    decode, the transform and the coders, its own allocations, fills and uploads, and the copies of statuses, histograms, lengths and
+    bytes that the host waits for -- is ordered on that stream (api._on_stream), whatever torch's current stream is.  The bytes returned
+    are complete.  (encode_coefficients on its own: the planes it is given must be ready for `stream`.)
+
     Raises jfif.JpegFormatError / jpeg_decode.JpegDecodeError for the input exactly as decode_jpeg does, ValueError for the arguments,
     api.MdctError if a coefficient cannot be written in a baseline scan (a DC difference beyond +-2047 can arise where blocks become
     neighbours that were not).
@@ -324,7 +331,7 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     mx, my = _ceil(sw, 8 * hmax), _ceil(sh, 8 * vmax)
     coefs = [p[:my * v * 8, :mx * h * 8] for p, (h, v) in zip(coefs, sampling)]
     if transform is not None:
-        with torch.cuda.device(coefs[0].device):
+        with torch.cuda.device(coefs[0].device), api._on_stream(stream, coefs[0].device):
             moved = []
             for p in coefs:
                 shape = (p.shape[1], p.shape[0]) if transform in TRANSPOSING else tuple(p.shape)
