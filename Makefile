@@ -1,6 +1,6 @@
 # Top-level build for C/C++ users (the Python entry point __graft_entry__.build() does the same).
 #   make            libmdct_hip.so + the C++ CLI + the CPU checker
-#   make lib | cli | jpeg_example | jpegcoef | jpegprog | jpegdec_prog | oracle | ref | clean
+#   make lib | cli | jpeg_example | jpegcoef | jpegprog | jpegdec_prog | jpegdec_batch | oracle | ref | clean
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := simd_dct_amd/csrc
@@ -51,6 +51,11 @@ simd_dct_amd/libmdct_jpegdec.so: $(CSRC)/jpeg_decode.hip $(HEADERS) $(LIB)
 simd_dct_amd/libmdct_jpegdec_prog.so: $(CSRC)/jpeg_decode_progressive.hip $(HEADERS) simd_dct_amd/libmdct_jpegdec.so
 	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_jpegdec -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
 
+# the restart-marked scans of many files in four launches (include/mdct_jpegdec_batch.h)
+jpegdec_batch: simd_dct_amd/libmdct_jpegdec_batch.so
+simd_dct_amd/libmdct_jpegdec_batch.so: $(CSRC)/jpeg_decode_batch.hip $(HEADERS) $(LIB)
+	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
+
 oracle:
 	$(MAKE) -C oracle
 ref:
@@ -60,4 +65,4 @@ clean:
 	rm -f $(LIB) tools/simd_dct_cli tools/mdct_jpeg
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib cli jpeg_example jpegcoef jpegprog jpegdec_prog oracle ref clean
+.PHONY: all lib cli jpeg_example jpegcoef jpegprog jpegdec_prog jpegdec_batch oracle ref clean

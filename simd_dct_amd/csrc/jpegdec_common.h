@@ -1,6 +1,7 @@
-// jpegdec_common.h -- what the two JPEG decoder libraries share (jpeg_decode.hip: restart-marked scans, libmdct_jpegdec.so;
-// jpeg_decode_unmarked.hip: scans without restart markers, libmdct_jpegdec_unmarked.so): the device Huffman tables and the handle
-// that owns them (huff_tables.h), the block layout (block_place.h), the bit reader with its unstuffing, the Huffman lookup, the
+// jpegdec_common.h -- what the JPEG decoder libraries share (jpeg_decode.hip: restart-marked scans, libmdct_jpegdec.so;
+// jpeg_decode_unmarked.hip: scans without restart markers, libmdct_jpegdec_unmarked.so; jpeg_decode_batch.hip: the restart-marked scans
+// of many files in one grid, libmdct_jpegdec_batch.so, which runs decode_interval and the index passes below as jpeg_decode.hip
+// does): the device Huffman tables and the handle that owns them (huff_tables.h), the block layout (block_place.h), the bit reader with its unstuffing, the Huffman lookup, the
 // sub-sequence decoder `run`, the skeleton both decoders hang it in -- a lane's sub-sequence (SubLane), the speculative first pass, the
 // settle loop that synchronises the lanes of a workgroup, the write pass -- the workgroup prefix sums and the host's descriptor checks.
 // Each library includes it from exactly one translation unit; everything here has internal linkage or is a device function.
@@ -510,6 +511,173 @@ __device__ __forceinline__ uint32_t write_pass(const DecArgs &a, const DevTables
   if (F.finished)
     *fin = F.fin;
   return unit0 + (uint32_t)F.blocks;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ one restart interval
+// The whole of k_decode (jpeg_decode.hip) for interval k of the scan `a` describes, run by one workgroup of kThreads lanes; k_decode_batch
+// (jpeg_decode_batch.hip) calls it with a scan record it looked up and the interval's index within that scan.  Everything that depends
+// on the interval's number -- its first MCU, RST(k mod 8), the `last` flag, off[k] / off[k + 1], status[k] -- is taken from k.
+__device__ __forceinline__ void decode_interval(const DecArgs &a, const uint32_t k)
+{
+  __shared__ DevTables T;
+  __shared__ uint32_t exit_state[kThreads];
+  __shared__ uint32_t lcomp[16];
+  __shared__ int wtot[kThreads / 64];
+  __shared__ uint32_t first_err, fin_word, fail_unit;
+  const int tid = threadIdx.x;
+  load_tables(a, T, lcomp, tid);
+  if (tid == 0)
+  {
+    first_err = kNone;
+    fin_word = kNone;
+  }
+  // the interval's data, clamped into the scan whatever the offsets say
+  const uint64_t len = a.scan_len;
+  const bool last = k + 1 == a.n_intervals;
+  uint64_t s = a.off[k];
+  const uint64_t next = a.off[k + 1];
+  uint64_t e = last ? next : (next >= 2 ? next - 2 : 0);
+  s = s < len ? s : len;
+  e = e < len ? e : len;
+  e = e > s ? e : s;
+  // T.81 B.1.1.2: 0xFF bytes directly before the interval's RSTm are fill bytes, not data (a data 0xFF is always followed by its
+  // stuffed zero).  The last interval's end is the scan's, which the caller gives without them.
+  if (!last && next <= len)
+    for (uint64_t i = 0, n = e - s; i < n && a.scan[e - 1] == 0xFF; i++)
+      e--;
+  const uint64_t sb = (e - s + kThreads - 1) / kThreads;
+  const SubLane q = sub_lane(s, e, sb < 8 ? 8 : sb, tid, true);
+  const uint32_t mcu0 = k * a.restart;
+  const uint32_t nmcu = (a.total_mcus - mcu0) < a.restart ? a.total_mcus - mcu0 : a.restart;
+  const uint32_t units = nmcu * a.g.upm;
+  wg_sync();
+
+  // ---- synchronisation: lane 0 starts exact, the others from a guess, until no start changes
+  Lane L;
+  uint32_t my_start = 0;
+  speculate(a, T, lcomp, q, my_start, L);
+  settle(a, T, lcomp, q, 0u, my_start, L, exit_state);
+
+  // ---- blocks before each lane's start, and the DC predictors there (an idle lane counts nothing)
+  const uint32_t unit0 = (uint32_t)wg_excl_scan(L.blocks, wtot);
+  int pred[3];
+  for (int c = 0; c < 3; c++)
+    pred[c] = wg_excl_scan(L.dc[c], wtot);
+
+  // ---- zero the interval's blocks.  The stores are numbered in 32 bits, whose division costs a fraction of the 64-bit one: units * 8 +
+  // kThreads stays below 2^32 for an interval of fewer than 2^29 - 32 blocks (64 GiB of coefficients), and this kernel has never
+  // zeroed a longer one
+  zero_units<uint32_t>(a.g, mcu0, 0, units, tid, kThreads);
+  __threadfence_block();
+  wg_sync();
+
+  // ---- the decode proper
+  uint32_t stop = 0;
+  if (q.active)
+    stop = write_pass(a, T, lcomp, q, my_start, unit0, units, mcu0, pred, &first_err, &fin_word);
+  wg_sync();
+  if (first_err != kNone)
+  {
+    // The lanes after the one that met the interval's first error started from states of the speculating passes, which carry on past
+    // such an error: what they wrote lies in blocks after the failing one and means nothing.  Those blocks go back to zero; the
+    // failing block keeps the levels decoded before the error (stop < units in the lane that reported it).
+    if ((uint32_t)tid == first_err >> 8)
+      fail_unit = stop;
+    __threadfence();
+    wg_sync();
+    zero_units<uint32_t>(a.g, mcu0, fail_unit + 1, units - (fail_unit + 1), tid, kThreads);
+  }
+  if (tid == 0)
+  {
+    uint32_t st = first_err != kNone ? (first_err & 0xFF) : (fin_word != kNone ? fin_word : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);
+    if (st == MDCT_JPEGDEC_OK && !last)
+    {
+      // the marker after the interval must be RST(k mod 8)
+      const bool ok = next >= 2 && next <= len && next - 2 >= s && a.scan[next - 2] == 0xFF && a.scan[next - 1] == 0xD0 + (k & 7);
+      if (!ok)
+        st = MDCT_JPEGDEC_UNEXPECTED_MARKER;
+    }
+    a.status[k] = st;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the index
+// One scan's restart markers -> the offsets of its intervals (mdct_jpegdec_index; the batch library runs the same three passes over
+// the chunks of many scans, each with the IndexArgs of its own scan).
+struct IndexArgs
+{
+  const uint8_t *scan;
+  uint64_t len, chunk;   // chunk: bytes per workgroup, a multiple of kThreads
+  uint32_t nchunks, n_intervals;
+  uint32_t *counts;      // [nchunks]: markers per chunk, then their exclusive prefix
+  uint64_t *off;
+};
+
+// host: the cut of mdct_jpegdec_index: chunks of at least 4096 bytes, a multiple of kThreads, and no more of them than intervals (the
+// counts live in the scan's status array)
+static inline void index_chunks(uint64_t scan_len, uint64_t n_intervals, IndexArgs &a)
+{
+  uint64_t chunk = (scan_len + n_intervals - 1) / n_intervals;
+  chunk = chunk < 4096 ? 4096 : chunk;
+  a.len = scan_len;
+  a.chunk = (chunk + kThreads - 1) / kThreads * kThreads;
+  a.nchunks = (uint32_t)((scan_len + a.chunk - 1) / a.chunk);
+  a.n_intervals = (uint32_t)n_intervals;
+}
+
+__device__ __forceinline__ bool rst_at(const uint8_t *scan, uint64_t len, uint64_t p)
+{
+  return scan[p] == 0xFF && p + 1 < len && (scan[p + 1] & 0xF8) == 0xD0;
+}
+
+// passes 1 (count) and 3 (WRITE) for chunk `chunk` of the scan, one workgroup of kThreads lanes
+template <bool WRITE>
+__device__ __forceinline__ void rst_walk(const IndexArgs &a, const uint32_t chunk)
+{
+  __shared__ int wtot[kThreads / 64];
+  __shared__ uint32_t base;
+  const uint64_t per = a.chunk / kThreads;
+  const uint64_t p0 = (uint64_t)chunk * a.chunk + threadIdx.x * per;
+  const uint64_t p1 = p0 + per < a.len ? p0 + per : a.len;
+  int n = 0;
+  for (uint64_t p = p0; p < p1; p++)
+    n += rst_at(a.scan, a.len, p);
+  if (!WRITE)
+  {
+    const int lane = threadIdx.x & 63;
+    const int tot = wave_incl_scan(n, lane);
+    if (lane == 63)
+      wtot[threadIdx.x >> 6] = tot;
+    wg_sync();
+    if (threadIdx.x == 0)
+      a.counts[chunk] = (uint32_t)(wtot[0] + wtot[1] + wtot[2] + wtot[3]);
+    return;
+  }
+  if (threadIdx.x == 0)
+    base = a.counts[chunk];
+  const int before = wg_excl_scan(n, wtot);
+  uint64_t j = (uint64_t)base + before; // ordinal of this lane's first marker
+  for (uint64_t p = p0; p < p1; p++)
+    if (rst_at(a.scan, a.len, p))
+    {
+      if (j + 1 < a.n_intervals)
+        a.off[j + 1] = p + 2;
+      j++;
+    }
+}
+
+// pass 2 for the scan, one workgroup of 1024 lanes
+__device__ __forceinline__ void rst_scan(const IndexArgs &a)
+{
+  __shared__ int wtot[16];
+  const uint32_t total = wg1024_excl_prefix(a.counts, a.counts, a.nchunks, wtot);
+  if (threadIdx.x == 0)
+  {
+    a.off[0] = 0;
+    a.off[a.n_intervals] = a.len;
+  }
+  for (uint64_t j = (uint64_t)total + threadIdx.x; j + 1 < a.n_intervals; j += 1024)
+    a.off[j + 1] = a.len + 2; // no marker: no data
 }
 
 } // namespace jpegdec

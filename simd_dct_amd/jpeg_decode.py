@@ -11,13 +11,15 @@ component's size (T.81 A.1.1).  With mode="RGB" the planes go through one more l
 With scale_denom = 2, 4 or 8 the picture comes out at 1/2, 1/4 or 1/8 size as libjpeg-turbo scales it (scaled_geometry): the scans are
 decoded as ever, components whose blocks shrink go through mdct_jpegscale_inv_i16_u8 (libmdct_jpegscale.so,
 include/mdct_jpegscale.h, loaded at the first such call) in place of the full inverse.
+decode_jpeg_batch decodes many files in one call: the restart-marked baseline scans of all of them in four launches
+(libmdct_jpegdec_batch.so, include/mdct_jpegdec_batch.h; BatchPlan), one inverse-DCT call over every plane, errors per file.
 torch is used for device memory and streams only.
 """
 import ctypes
 
 import numpy as np
 
-from . import _jpegcolor_lib, _jpegdec_lib, _jpegdec_prog_lib, _jpegdec_unmarked_lib, api, jfif
+from . import _jpegcolor_lib, _jpegdec_batch_lib, _jpegdec_lib, _jpegdec_prog_lib, _jpegdec_unmarked_lib, api, jfif
 from .api import _ptr, _stream
 
 
@@ -397,6 +399,242 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
             out = to_rgb(out, [(c["h"], c["v"]) for c in info["components"]], info["width"], info["height"], colour=info["colorspace"],
                          layout=layout, stream=stream)
     return (out, coefs) if coefficients else out
+
+
+def batch_last_error():
+    return _jpegdec_batch_lib.load().mdct_jpegdec_batch_last_error().decode()
+
+
+class BatchPlan:
+    """mdct_jpegdec_batch_plan: the host's plan of a batch of restart-marked baseline scans (include/mdct_jpegdec_batch.h); no device
+    is needed to make one.  scans: list of (desc, byte_offset, byte_len, specs) -- desc as scan_desc() builds it, the scan's bytes at
+    [byte_offset, byte_offset + byte_len) of the batch's byte buffer of total_bytes, specs = 4 x (bits16, vals) or None.
+    MdctError (.scan: the scan refused, None for the batch as a whole) with the single-scan library's message for what it refuses."""
+
+    def __init__(self, scans, total_bytes):
+        lib = _jpegdec_batch_lib.load()
+        arr = (_jpegdec_batch_lib.BatchScan * max(1, len(scans)))()
+        keep = []
+        for i, (desc, off, length, specs) in enumerate(scans):
+            b, v, n, k = _spec_arrays(specs)
+            keep.append(k)
+            arr[i].desc, arr[i].byte_offset, arr[i].byte_len = desc, off, length
+            for t in range(4):
+                arr[i].bits16[t], arr[i].vals[t], arr[i].nvals[t] = b[t], v[t], n[t]
+        h, bad = ctypes.c_void_p(), ctypes.c_size_t()
+        rc = lib.mdct_jpegdec_batch_plan_create(ctypes.byref(h), arr, len(scans), total_bytes, ctypes.byref(bad))
+        if rc != 0:
+            e = api.MdctError(f"mdct_jpegdec_batch status {rc}: {batch_last_error()}")
+            e.scan = bad.value if bad.value < len(scans) else None
+            raise e
+        self.handle, self._lib = h, lib
+        self.n_scans = int(lib.mdct_jpegdec_batch_scans(h))
+        self.n_intervals = int(lib.mdct_jpegdec_batch_intervals(h))
+        self.n_offsets = int(lib.mdct_jpegdec_batch_offsets(h))
+        self.n_chunks = int(lib.mdct_jpegdec_batch_chunks(h))
+        self.n_table_sets = int(lib.mdct_jpegdec_batch_table_sets(h))
+        self.image_bytes = int(lib.mdct_jpegdec_batch_image_bytes(h))
+        self.first_interval = [int(lib.mdct_jpegdec_batch_first_interval(h, i)) for i in range(self.n_scans + 1)]
+
+    @property
+    def first_chunk(self):
+        """the prefix of the scans' index chunk counts"""
+        return [int(self._lib.mdct_jpegdec_batch_first_chunk(self.handle, i)) for i in range(self.n_scans + 1)]
+
+    @property
+    def chunk_bytes(self):
+        """the chunk size mdct_jpegdec_index cuts each scan by"""
+        return [int(self._lib.mdct_jpegdec_batch_chunk_bytes(self.handle, i)) for i in range(self.n_scans)]
+
+    @property
+    def table_set(self):
+        """the table set of each scan"""
+        return [int(self._lib.mdct_jpegdec_batch_table_set(self.handle, i)) for i in range(self.n_scans)]
+
+    def chunk_scan(self):
+        """the chunk table: the scan every index chunk of the batch belongs to"""
+        return [int(self._lib.mdct_jpegdec_batch_chunk_scan(self.handle, c)) for c in range(self.n_chunks)]
+
+    def _rc(self, rc):
+        if rc != 0:
+            raise api.MdctError(f"mdct_jpegdec_batch status {rc}: {batch_last_error()}")
+
+    def bind(self, device_image, scan_bytes, offsets, status):
+        """mdct_jpegdec_batch_bind: -> the image as a numpy uint8 array, to be copied to device_image (a device tensor of image_bytes
+        bytes) before the first launch.  offsets: n_offsets int64, status: n_intervals int32 device tensors."""
+        host = np.zeros(self.image_bytes, dtype=np.uint8)
+        self._rc(self._lib.mdct_jpegdec_batch_bind(self.handle, host.ctypes.data, _ptr(device_image), _ptr(scan_bytes), _ptr(offsets), _ptr(status)))
+        return host
+
+    def index(self, stream=None):
+        """mdct_jpegdec_batch_index: three launches"""
+        self._rc(self._lib.mdct_jpegdec_batch_index(self.handle, _stream(stream)))
+
+    def decode(self, stream=None):
+        """mdct_jpegdec_batch_decode: one launch"""
+        self._rc(self._lib.mdct_jpegdec_batch_decode(self.handle, _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            self._lib.mdct_jpegdec_batch_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _PlaneShape:
+    """stands for a coefficient plane that is not allocated yet where scan_plan only looks at a plane's address and pitch"""
+
+    def __init__(self, rows, cols, address=256):
+        self.shape, self._address = (rows, cols), address
+
+    def data_ptr(self):
+        return self._address
+
+
+_ON_ERROR = ("raise", "return")
+_ARENA_ALIGN = 256  # bytes between the starts of two planes of an arena, at least
+
+
+def decode_jpeg_batch(files, device=None, stream=None, *, mode=None, layout="HWC", coefficients=False, on_error="raise"):
+    """Decode a sequence of JPEG files (bytes) on the GPU: a list with one entry per file, each exactly what decode_jpeg(file, device,
+    coefficients, stream, mode=mode, layout=layout) returns.  Accepts whatever decode_jpeg accepts (scale_denom excepted).
+    Files whose every scan is baseline with restart markers take the batch path (libmdct_jpegdec_batch.so,
+    include/mdct_jpegdec_batch.h): every file is parsed and every scan planned on the host first; then one upload of all scans' bytes,
+    one of the scan records and Huffman table sets (equal tables stored once), one zeroed int16 arena for all coefficient planes and one
+    uint8 arena for all pixel planes, four launches for the entropy stage of the whole batch (three index passes, one decode with a
+    workgroup per restart interval), ONE copy of all interval statuses to the host, and one api.u8_i16_batch("inv", ...) over the
+    planes of all files that decoded cleanly.  mode="RGB" then converts file by file (to_rgb): a batched colour kernel is out of scope.
+    The tensors one call returns for batch-path files are views of those arenas: they share storage, and keeping one keeps the
+    arena of the whole batch alive.  A file with a scan without restart markers, or a progressive file, goes through decode_jpeg on
+    its own inside the call, on the same stream.
+    Errors are per file and never change another file's output.  on_error="raise": the exception of the lowest-numbered failing file
+    is raised, of the type and with the message decode_jpeg gives for that file alone (jfif.JpegFormatError; JpegDecodeError with .scan
+    and .status; api.MdctError), with the added attribute .file, the file's index.  on_error="return": that exception object stands in
+    the file's slot, every other file is decoded.  An empty sequence returns [] without touching the device.
+    stream: as for decode_jpeg -- every launch, allocation, fill, upload and the status copy of the call is ordered on it."""
+    if mode not in (None, "RGB"):
+        raise ValueError(f"mode {mode!r} (None or 'RGB')")
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r} ('HWC' or 'CHW')")
+    if on_error not in _ON_ERROR:
+        raise ValueError(f"on_error {on_error!r} ('raise' or 'return')")
+    files = list(files)
+    if not files:
+        return []
+    results = [None] * len(files)
+
+    def failed(i, e):
+        e.file = i
+        results[i] = e
+
+    # ---- host: parse every file, plan every scan (against planes that stand for the arena's)
+    # batch path: (file index, info, geo, [(int16 arena element, uint8 arena byte) every plane starts at], [(specs, desc) per scan])
+    jobs, singles = [], []
+    n_coef = n_px = 0
+    for i, data in enumerate(files):
+        try:
+            info = read_file(data)
+            if mode == "RGB":
+                _colour_params(info)
+            if info["sof"] == 0xC2 or any(sc["restart_interval"] == 0 for sc in info["scans"]):
+                singles.append(i)
+                continue
+            geo, grid = geometry(info)
+            stand_in = [_PlaneShape(by * 8, bx * 8) for _, _, bx, by in geo]
+            plans = [scan_plan(info, si, sc, geo, grid, stand_in) for si, sc in enumerate(info["scans"])]
+        except (jfif.JpegFormatError, api.MdctError) as e:
+            failed(i, e)
+            continue
+        at = []
+        for _, _, bx, by in geo:
+            at.append((n_coef, n_px))
+            n_coef += _ceil(by * bx * 64 * 2, _ARENA_ALIGN) * _ARENA_ALIGN // 2
+            n_px += _ceil(by * bx * 64, _ARENA_ALIGN) * _ARENA_ALIGN
+        jobs.append((i, info, geo, at, plans))
+    if jobs or singles:
+        import torch
+
+        dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+    # ---- files outside the batch path, one at a time
+    for i in singles:
+        try:
+            results[i] = decode_jpeg(files[i], dev, coefficients, stream, mode=mode, layout=layout)
+        except (jfif.JpegFormatError, JpegDecodeError, api.MdctError) as e:
+            failed(i, e)
+    if jobs:
+        _decode_batch_path(torch, files, jobs, (n_coef, n_px), results, failed, dev, stream, mode, layout, coefficients)
+    if on_error == "raise":
+        for r in results:
+            if isinstance(r, Exception):
+                raise r  # the lowest-numbered failing file's, whichever stage found it
+    return results
+
+
+def _decode_batch_path(torch, files, jobs, arena, results, failed, dev, stream, mode, layout, coefficients):
+    """the batch path of decode_jpeg_batch for the files `jobs` names (planned and found acceptable already; arena: the sizes of the two
+    arenas their planes were placed in)"""
+    with torch.cuda.device(dev), api._on_stream(stream, dev):
+        n_coef, n_px = arena  # elements of the int16 arena, bytes of the uint8 one
+        coef_arena = torch.zeros(n_coef, dtype=torch.int16, device=dev)
+        px_arena = torch.empty(n_px, dtype=torch.uint8, device=dev)
+        blob, coefs, pxs, scans, owner = bytearray(), {}, {}, [], []
+        for i, info, geo, at, plans in jobs:
+            coefs[i] = [coef_arena[c0:c0 + by * bx * 64].view(by * 8, bx * 8) for (c0, _), (_, _, bx, by) in zip(at, geo)]
+            pxs[i] = [px_arena[p0:p0 + by * bx * 64].view(by * 8, bx * 8) for (_, p0), (_, _, bx, by) in zip(at, geo)]
+            raw = bytes(files[i])
+            for si, (sc, (specs, desc)) in enumerate(zip(info["scans"], plans)):
+                for c, member in enumerate(sc["components"]):  # the planes the descriptor was checked against, now where they are
+                    desc.comp[c].coef = _ptr(coefs[i][member["index"]])
+                scans.append((desc, len(blob), sc["end"] - sc["start"], specs))
+                owner.append((i, si))
+                blob += raw[sc["start"]:sc["end"]]
+        seg = torch.frombuffer(blob or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
+        plan = BatchPlan(scans, len(blob))
+        try:
+            off = torch.empty(plan.n_offsets, dtype=torch.int64, device=dev)
+            status = torch.empty(plan.n_intervals, dtype=torch.int32, device=dev)
+            image = torch.empty(plan.image_bytes, dtype=torch.uint8, device=dev)  # the caching allocator's blocks are 512-byte aligned
+            image.copy_(torch.from_numpy(plan.bind(image, seg, off, status)))
+            plan.index(stream)
+            plan.decode(stream)
+            st = status.cpu().numpy()  # the call's one wait for the device
+            first = plan.first_interval
+        finally:
+            plan.close()
+        for k, (i, si) in enumerate(owner):
+            if isinstance(results[i], Exception):
+                continue  # an earlier scan of the file failed: decode_jpeg stops there
+            s = st[first[k]:first[k + 1]].copy()
+            bad = np.flatnonzero(s)
+            if bad.size:
+                j = int(bad[0])
+                failed(i, JpegDecodeError(f"scan {si}: {bad.size} of {s.size} restart intervals failed; "
+                                          f"interval {j}: {STATUS_NAMES.get(int(s[j]), int(s[j]))}", scan=si, status=s))
+        planes = []
+        for i, info, geo, _, _ in jobs:
+            if isinstance(results[i], Exception):
+                continue
+            try:
+                luts = component_luts(info)
+            except jfif.JpegFormatError as e:
+                failed(i, e)
+                continue
+            planes += [(p, q, g[2] * 8, g[3] * 8, lut) for p, q, g, lut in zip(pxs[i], coefs[i], geo, luts)]
+        if planes:
+            api.u8_i16_batch("inv", planes, level_shift=True, stream=stream)
+        for i, info, geo, _, _ in jobs:
+            if isinstance(results[i], Exception):
+                continue
+            out = [p[:g[1], :g[0]] for p, g in zip(pxs[i], geo)]
+            if mode == "RGB":
+                out = to_rgb(out, [(c["h"], c["v"]) for c in info["components"]], info["width"], info["height"], colour=info["colorspace"],
+                             layout=layout, stream=stream)
+            results[i] = (out, coefs[i]) if coefficients else out
 
 
 _COLOURS = {"YCbCr": _jpegcolor_lib.YCBCR, "RGB": _jpegcolor_lib.RGB, "grey": _jpegcolor_lib.GREY}
