@@ -1,6 +1,6 @@
 # Top-level build for C/C++ users (the Python entry point __graft_entry__.build() does the same).
 #   make            libmdct_hip.so + the C++ CLI + the CPU checker
-#   make lib | cli | jpeg_example | jpegcoef | jpegprog | jpegdec_prog | jpegdec_batch | oracle | ref | clean
+#   make lib | cli | jpeg_example | jpegcoef | jpegprog | jpegdec_prog | jpegdec_batch | jpegenc_batch | oracle | ref | clean
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := simd_dct_amd/csrc
@@ -56,6 +56,11 @@ jpegdec_batch: simd_dct_amd/libmdct_jpegdec_batch.so
 simd_dct_amd/libmdct_jpegdec_batch.so: $(CSRC)/jpeg_decode_batch.hip $(HEADERS) $(LIB)
 	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
 
+# many RGB images -> their interleaved scans in three launches (include/mdct_jpegenc_batch.h)
+jpegenc_batch: simd_dct_amd/libmdct_jpegenc_batch.so
+simd_dct_amd/libmdct_jpegenc_batch.so: $(CSRC)/jpeg_encode_batch.hip $(HEADERS) $(LIB)
+	$(HIPCC) $(HIPFLAGS) -shared $< -ldl -Lsimd_dct_amd -lmdct_hip -Wl,-rpath,'$$ORIGIN' -o $@
+
 oracle:
 	$(MAKE) -C oracle
 ref:
@@ -65,4 +70,4 @@ clean:
 	rm -f $(LIB) tools/simd_dct_cli tools/mdct_jpeg
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib cli jpeg_example jpegcoef jpegprog jpegdec_prog jpegdec_batch oracle ref clean
+.PHONY: all lib cli jpeg_example jpegcoef jpegprog jpegdec_prog jpegdec_batch jpegenc_batch oracle ref clean

@@ -10,11 +10,9 @@
 // a barrier.  The layouts and the scan order are scan_order.h's, the transform phase and the read-out of a thread's block in scan
 // order scan_chunks.h's: both are shared with k_opt (jpeg_encode_opt.hip).  This kernel's own are the LDS, the Annex K tables and the
 // bit-stream ring, the coding phase (HuffSeqCoder16, huffman_rows.h) and the epilogue.  The host checks it shares with
-// jpeg_encode_opt.hip are scan_host.h's.
+// jpeg_encode_opt.hip, and the Annex K codes it shares with jpeg_encode_batch.hip, are scan_host.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <mutex>
 
 #include "aan_passes.h" // aan_fwd_h, aan_fwd_v, fwd_v_quant_levels, compact_levels16
 #include "host_error.h"
@@ -110,40 +108,6 @@ __global__ __launch_bounds__((64 * kWaves<H, V>)) void k_scan_rows(ScanArgs a)
 } // namespace mdct
 
 using namespace mdct::jpegenc_scan;
-
-namespace
-{
-
-// size << 16 | code of every symbol of the four Annex K tables (T.81 Annex C from mdct_huffman_spec), built once per process
-struct HuffCodes
-{
-  uint32_t dc[2][12], ac[2][256];
-  bool ok;
-};
-
-const HuffCodes &huff_codes()
-{
-  static HuffCodes t;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    memset(&t, 0, sizeof(t));
-    t.ok = true;
-    for (int which = 0; which < 4; which++)
-    { // 0 DC luminance, 1 AC luminance, 2 DC chrominance, 3 AC chrominance
-      uint8_t bits[16], vals[256];
-      int nvals = 0;
-      if (mdct_huffman_spec(which, bits, vals, &nvals) != MDCT_SUCCESS)
-      {
-        t.ok = false;
-        return;
-      }
-      annex_c_codes(bits, vals, nvals, (which & 1) ? 256 : 12, (which & 1) ? t.ac[which >> 1] : t.dc[which >> 1]);
-    }
-  });
-  return t;
-}
-
-} // namespace
 
 extern "C" {
 

@@ -34,20 +34,32 @@ struct ChunkBlock
   bool eob;
 };
 
-// Args: the kernel's argument struct, with mcus_x.  The kernel's own type, not a common base: a source may read its tables at
-// offsetof(Args, ...) of the argument segment.
-template <int H, int V, class Args>
+// Args: the kernel's argument struct.  The kernel's own type, not a common base: a source may read its tables at offsetof(Args, ...)
+// of the argument segment.  The row's length in MCUs is Args' mcus_x where a launch codes one image; OwnRow: a kernel whose workgroups
+// code rows of different images (k_batch_scan_rows, jpeg_encode_batch.hip) gives each workgroup its own, and Args has none.
+template <int H, int V, class Args, bool OwnRow = false>
 struct ChunkGrid
 {
   static constexpr uint32_t kThreads = 64 * scan_order::kWaves<H, V>, M = scan_order::kMcus<H, V>;
   static_assert(kThreads == M * scan_order::kBlocksPerMcu<H, V>, "one symbols thread per block of the chunk");
 
   const Args &a;
+  uint32_t own_mcus_x; // OwnRow only
   uint32_t tid, bx0, step, last_blk;
   uint16_t *rec;              // this lane's LDS row
   uint32_t (*meta)[kThreads]; // DC (low 16 bits) | entries << 16 | EOB needed << 24, by slot; [chunk parity]
 
-  __device__ __forceinline__ explicit ChunkGrid(const Args &a_) : a(a_) {}
+  __device__ __forceinline__ explicit ChunkGrid(const Args &a_) : a(a_) { static_assert(!OwnRow, "an OwnRow grid is given its row's length"); }
+  __device__ __forceinline__ ChunkGrid(const Args &a_, uint32_t mcus_x_) : a(a_), own_mcus_x(mcus_x_) { static_assert(OwnRow, "Args' mcus_x is the row's length"); }
+
+  // MCUs in the row this workgroup codes
+  __device__ __forceinline__ uint32_t row_mcus() const
+  {
+    if constexpr (OwnRow)
+      return own_mcus_x;
+    else
+      return a.mcus_x;
+  }
 
   // the transform phase's block of this thread: component, block row of its plane, first block and blocks per chunk
   __device__ __forceinline__ void place(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[kThreads], uint32_t &comp,
@@ -61,7 +73,7 @@ struct ChunkGrid
       comp = 0;
       bx0 = tid;
       step = 256;
-      last_blk = a.mcus_x - 1;
+      last_blk = row_mcus() - 1;
       brow = my;
     }
     else if (H == 1)
@@ -69,7 +81,7 @@ struct ChunkGrid
       comp = wave;
       bx0 = lane;
       step = 64;
-      last_blk = a.mcus_x - 1;
+      last_blk = row_mcus() - 1;
       brow = my;
     }
     else if (!chroma_wave)
@@ -77,7 +89,7 @@ struct ChunkGrid
       comp = 0;
       bx0 = lane;
       step = 64;
-      last_blk = 2 * a.mcus_x - 1;
+      last_blk = 2 * row_mcus() - 1;
       brow = my * V + wave;
     }
     else
@@ -85,7 +97,7 @@ struct ChunkGrid
       comp = 1 + (lane >> 5);
       bx0 = lane & 31;
       step = 32;
-      last_blk = a.mcus_x - 1;
+      last_blk = row_mcus() - 1;
       brow = my;
     }
     rec = rec_all + tid * kRec16Row;
@@ -106,7 +118,7 @@ struct ChunkGrid
     const uint32_t me = meta[par][sb.slot];
     ChunkBlock b;
     b.n = (int)((me >> 16) & 0xFFu);
-    b.live = m0 + sb.mcu < a.mcus_x;
+    b.live = m0 + sb.mcu < row_mcus();
     b.dc = (int)(int16_t)(me & 0xFFFFu);
     b.pred = sb.carry ? (m0 == 0 ? 0 : (int)(int16_t)(meta[par ^ 1][sb.pred] & 0xFFFFu)) : (int)(int16_t)(meta[par][sb.pred] & 0xFFFFu);
     b.eob = (me >> 24) != 0;
@@ -114,12 +126,13 @@ struct ChunkGrid
   }
 };
 
-// The pixel source.  Args: with px[3], pitch[3], tb[2], consts, mcus_x and dc_shift (ScanArgs, OptArgs); the multiplier pairs are read
-// at offsetof(Args, tb) of the argument segment.
-template <int H, int V, class Args>
-struct ScanChunks : ChunkGrid<H, V, Args>
+// The pixel source.  Args: with tb[2], consts and dc_shift, and px[3], pitch[3], mcus_x where a launch codes one image (ScanArgs,
+// OptArgs); the multiplier pairs are read at offsetof(Args, tb) of the argument segment.  A kernel whose workgroups code rows of
+// different images (OwnRow) passes the row's length to the constructor and its image's planes to init.
+template <int H, int V, class Args, bool OwnRow = false>
+struct ScanChunks : ChunkGrid<H, V, Args, OwnRow>
 {
-  using Grid = ChunkGrid<H, V, Args>;
+  using Grid = ChunkGrid<H, V, Args, OwnRow>;
   using Grid::a;
   using Grid::bx0;
   using Grid::last_blk;
@@ -133,6 +146,7 @@ struct ScanChunks : ChunkGrid<H, V, Args>
   karg_pairs_t qf;
 
   __device__ __forceinline__ explicit ScanChunks(const Args &a_) : Grid(a_) {}
+  __device__ __forceinline__ ScanChunks(const Args &a_, uint32_t mcus_x_) : Grid(a_, mcus_x_) {}
 
   // the 8 rows of block min(bx, last) of the block row (lanes past the row's end redo the last block)
   __device__ __forceinline__ void fetch(uint32_t bx)
@@ -146,12 +160,17 @@ struct ScanChunks : ChunkGrid<H, V, Args>
   // the transform phase's block of this thread (ChunkGrid::place) in its plane; its first rows are requested
   __device__ __forceinline__ void init(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[Grid::kThreads])
   {
+    init(tid_, lane, wave, my, rec_all, meta_, a.px[0], a.px[1], a.px[2], a.pitch[0], a.pitch[1], a.pitch[2]);
+  }
+
+  // ... in the planes given (wave-uniform values)
+  __device__ __forceinline__ void init(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[Grid::kThreads],
+                                       const uint8_t *px0, const uint8_t *px1, const uint8_t *px2, size_t pitch0, size_t pitch1, size_t pitch2)
+  {
     uint32_t comp, brow;
     bool chroma_wave;
     Grid::place(tid_, lane, wave, my, rec_all, meta_, comp, brow, chroma_wave);
     // (selects, not an index: the argument block stays in scalar registers)
-    const size_t pitch0 = a.pitch[0], pitch1 = a.pitch[1], pitch2 = a.pitch[2];
-    const uint8_t *const px0 = a.px[0], *const px1 = a.px[1], *const px2 = a.px[2];
     pitch = comp == 0 ? pitch0 : comp == 1 ? pitch1 : pitch2;
     src_row = (comp == 0 ? px0 : comp == 1 ? px1 : px2) + (size_t)brow * 8 * pitch;
     fetch(bx0);
@@ -177,7 +196,7 @@ struct ScanChunks : ChunkGrid<H, V, Args>
     uint32_t val[64];
     fwd_v_quant_levels<true>(K, P, qf, a.dc_shift, val);
     Grid::leave(val, par);
-    if (m0 + M < a.mcus_x)
+    if (m0 + M < Grid::row_mcus())
       fetch(bx0 + (chunk + 1) * step);
   }
 };

@@ -1,9 +1,11 @@
 // scan_host.h -- host checks and table building shared by the JPEG scan coders' entry points (jpeg_encode_scan.hip,
-// jpeg_encode_opt.hip).  Include after host_error.h: every check leaves its message through that translation unit's fail().
+// jpeg_encode_opt.hip, jpeg_encode_batch.hip).  Include after host_error.h: every check leaves its message through that translation unit's fail().
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+
+#include <mutex>
 
 #include "mdct_jpegenc_opt.h"
 #include "mdct_jpegenc_scan.h"
@@ -79,6 +81,35 @@ void annex_c_codes(const uint8_t *bits16, const uint8_t *vals, int nvals, int ca
     for (int i = 0; i < bits16[len - 1] && k < nvals; i++, k++, code++)
       if (vals[k] < cap)
         tab[vals[k]] = len << 16 | code;
+}
+
+// size << 16 | code of every symbol of the four Annex K tables (T.81 Annex C from mdct_huffman_spec), built once per process
+struct HuffCodes
+{
+  uint32_t dc[2][12], ac[2][256];
+  bool ok;
+};
+
+[[maybe_unused]] const HuffCodes &huff_codes()
+{
+  static HuffCodes t;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    memset(&t, 0, sizeof(t));
+    t.ok = true;
+    for (int which = 0; which < 4; which++)
+    { // 0 DC luminance, 1 AC luminance, 2 DC chrominance, 3 AC chrominance
+      uint8_t bits[16], vals[256];
+      int nvals = 0;
+      if (mdct_huffman_spec(which, bits, vals, &nvals) != MDCT_SUCCESS)
+      {
+        t.ok = false;
+        return;
+      }
+      annex_c_codes(bits, vals, nvals, (which & 1) ? 256 : 12, (which & 1) ? t.ac[which >> 1] : t.dc[which >> 1]);
+    }
+  });
+  return t;
 }
 
 // a specification -> size << 16 | code per symbol (T.81 Annex C); checked as mdct_jpegdec_tables_check checks one, and no symbol twice.

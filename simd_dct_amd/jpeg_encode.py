@@ -10,11 +10,15 @@ MCU order; one packing launch and one read-back instead of three).
 With optimize=True the Huffman tables are made for the image (T.81 K.2, libjpeg's optimize_coding; libmdct_jpegenc_opt.so,
 include/mdct_jpegenc_opt.h): symbol_histogram counts the symbols the coder will emit, optimal_tables builds the tables on the host and
 the coders of that library take them in place of the Annex K ones.
+encode_jpeg_batch writes many colour images as interleaved files in three launches (libmdct_jpegenc_batch.so,
+include/mdct_jpegenc_batch.h): the mirror of jpeg_decode.decode_jpeg_batch.
 torch is used for device memory and streams only.
 """
+import ctypes
+
 import numpy as np
 
-from . import _jpegenc_lib, _jpegenc_opt_lib, _jpegenc_scan_lib, api, jfif
+from . import _jpegenc_batch_lib, _jpegenc_lib, _jpegenc_opt_lib, _jpegenc_scan_lib, api, jfif
 from .api import _stream
 
 # ITU-T T.81 Annex K.1 / K.2 (natural order v*8+u)
@@ -94,6 +98,19 @@ def _image_shape(image, layout):
     return H, W, grey
 
 
+def _input_of(image, layout, grey=False):
+    """(pitch, plane stride) of a tensor the front kernels read in place: contiguous innermost dimension, HWC pixels of 3 contiguous bytes"""
+    if grey:
+        ok, pitch, stride = image.stride(1) == 1, image.stride(0), 0
+    elif layout == "HWC":
+        ok, pitch, stride = image.stride(2) == 1 and image.stride(1) == 3, image.stride(0), 0
+    else:
+        ok, pitch, stride = image.stride(2) == 1, image.stride(1), image.stride(0)
+    if not ok:
+        raise ValueError("image: contiguous innermost dimension (HWC: 3 contiguous bytes per pixel)")
+    return pitch, stride
+
+
 def to_planes(image, subsampling="4:2:0", layout="HWC", planes=None, stream=None):
     """mdct_jpegenc_from_rgb on a device tensor.  image: uint8 [H, W, 3] (HWC), [3, H, W] (CHW) or [H, W] (grey); its rows (and CHW
     planes) may lie any pitch apart, the innermost dimension must be contiguous (HWC: pixels of 3 contiguous bytes).  planes: uint8
@@ -106,17 +123,7 @@ def to_planes(image, subsampling="4:2:0", layout="HWC", planes=None, stream=None
         raise ValueError("image: a uint8 device tensor")
     sampling = sampling_of(subsampling, grey)
     sizes = component_sizes(W, H, sampling)
-    if grey:
-        ok = image.stride(1) == 1
-        pitch, stride = image.stride(0), 0
-    elif layout == "HWC":
-        ok = image.stride(2) == 1 and image.stride(1) == 3
-        pitch, stride = image.stride(0), 0
-    else:
-        ok = image.stride(2) == 1
-        pitch, stride = image.stride(1), image.stride(0)
-    if not ok:
-        raise ValueError("image: contiguous innermost dimension (HWC: 3 contiguous bytes per pixel)")
+    pitch, stride = _input_of(image, layout, grey)
     if planes is None:
         with api._on_stream(stream, image.device):
             planes = [torch.empty((ph, pw), dtype=torch.uint8, device=image.device) for _, _, pw, ph in sizes]
@@ -440,3 +447,240 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
             raise api.MdctError(f"{int(uncoded.item())} symbols of the scans have no code in the tables made for them")
         comps = [dict(scan=sc.out[:n].cpu().numpy(), blocks_per_row=pw // 8, qtable=t) for sc, n, (_, _, pw, _), t in zip(scans, ends, sizes, tabs)]
     return jfif.write_jpeg(comps, W, H, specs=specs, sampling=sampling)
+
+
+def batch_last_error():
+    return _jpegenc_batch_lib.load().mdct_jpegenc_batch_last_error().decode()
+
+
+class BatchPlan:
+    """mdct_jpegenc_batch_plan: the host's plan of a batch of colour images (include/mdct_jpegenc_batch.h); no device is needed to make
+    one, the addresses are only compared.  images: list of (address, pitch, plane stride, width, height, planes, segment address,
+    seg_stride) with planes = 3 x (address, pitch, padded width, padded height, h, v) on the MCU grid; layout 'HWC' or 'CHW'; luts:
+    (luma, chroma), 64 numbers each in natural order.  MdctError (.image: the image refused, None for the batch as a whole) with the
+    single-image libraries' messages for what they refuse."""
+
+    def __init__(self, images, layout, luts):
+        lib = _jpegenc_batch_lib.load()
+        arr = (_jpegenc_batch_lib.BatchImage * max(1, len(images)))()
+        for i, (address, pitch, stride, width, height, planes, seg, seg_stride) in enumerate(images):
+            arr[i].in_, arr[i].in_pitch, arr[i].in_plane_stride, arr[i].width, arr[i].height = address, pitch, stride, width, height
+            for k, p in enumerate(planes):
+                arr[i].planes[k] = _jpegenc_lib.Plane(*p)
+            arr[i].seg, arr[i].seg_stride = seg, seg_stride
+        tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+        h, bad = ctypes.c_void_p(), ctypes.c_size_t()
+        rc = lib.mdct_jpegenc_batch_plan_create(ctypes.byref(h), arr, len(images), _LAYOUTS[layout], tabs[0].ctypes.data, tabs[1].ctypes.data, ctypes.byref(bad))
+        if rc != 0:
+            e = api.MdctError(f"mdct_jpegenc_batch status {rc}: {batch_last_error()}")
+            e.image = bad.value if bad.value < len(images) else None
+            raise e
+        self.handle, self._lib = h, lib
+        self.n_images = int(lib.mdct_jpegenc_batch_images(h))
+        self.n_rows = int(lib.mdct_jpegenc_batch_rows(h))
+        self.n_tiles = int(lib.mdct_jpegenc_batch_tiles(h))
+        self.image_bytes = int(lib.mdct_jpegenc_batch_image_bytes(h))
+        self.first_row = [int(lib.mdct_jpegenc_batch_first_row(h, i)) for i in range(self.n_images + 1)]
+        self.first_tile = [int(lib.mdct_jpegenc_batch_first_tile(h, i)) for i in range(self.n_images + 1)]
+
+    def row_table(self):
+        """the packer's row table: (image, 1 if the row is its image's last, m of the RSTm after it) per MCU row of the batch"""
+        lib, h = self._lib, self.handle
+        return [(int(lib.mdct_jpegenc_batch_row_image(h, r)), int(lib.mdct_jpegenc_batch_row_last(h, r)), int(lib.mdct_jpegenc_batch_row_marker(h, r)))
+                for r in range(self.n_rows)]
+
+    def _rc(self, rc):
+        if rc != 0:
+            raise api.MdctError(f"mdct_jpegenc_batch status {rc}: {batch_last_error()}")
+
+    def bind(self, device_image, seg_bytes, ff_counts):
+        """mdct_jpegenc_batch_bind: -> the image as a numpy uint8 array, to be copied to device_image (a device tensor of image_bytes
+        bytes) before the first launch.  seg_bytes, ff_counts: n_rows int32 device tensors each."""
+        host = np.zeros(self.image_bytes, dtype=np.uint8)
+        self._rc(self._lib.mdct_jpegenc_batch_bind(self.handle, host.ctypes.data, api._ptr(device_image), api._ptr(seg_bytes), api._ptr(ff_counts)))
+        return host
+
+    def planes(self, stream=None):
+        """mdct_jpegenc_batch_planes: one launch"""
+        self._rc(self._lib.mdct_jpegenc_batch_planes(self.handle, _stream(stream)))
+
+    def scan(self, stream=None):
+        """mdct_jpegenc_batch_scan: one launch"""
+        self._rc(self._lib.mdct_jpegenc_batch_scan(self.handle, _stream(stream)))
+
+    def pack(self, out, row_offsets, stream=None):
+        """mdct_jpegenc_batch_pack: one launch.  out: uint8 device tensor (its size is the capacity); row_offsets: n_rows + 1 int64"""
+        self._rc(self._lib.mdct_jpegenc_batch_pack(self.handle, api._ptr(out), out.numel(), api._ptr(row_offsets), _stream(stream)))
+
+    def close(self):
+        if self.handle:
+            self._lib.mdct_jpegenc_batch_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_ARENA_ALIGN = 256  # bytes between the starts of two images, planes or segment ranges of an arena, at least
+
+
+def _align(n):
+    return _ceil(n, _ARENA_ALIGN) * _ARENA_ALIGN
+
+
+def encode_jpeg_batch(images, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None):
+    """Encode a sequence of 8-bit images as baseline JPEG files on the GPU: a list of bytes, file i byte for byte what
+    encode_jpeg(images[i], quality, subsampling, layout, interleaved=True) returns.  The mirror of jpeg_decode.decode_jpeg_batch.
+
+    images: uint8 images of any sizes, each [H, W, 3] (layout="HWC"), [3, H, W] (layout="CHW") or [H, W] (grey) -- numpy arrays, CPU
+    tensors and device tensors in any mix (device tensors on one device; views with a pitch are used in place) -- or one 4-D array or
+    tensor, taken as the sequence of its slices.  One quality, subsampling and layout per call.  Every image's arguments are checked
+    before any device work: the checks are encode_jpeg's and raise ValueError with its messages and the added attribute .file, the
+    image's index.  An empty sequence returns [] without touching the device.
+
+    All colour images go through THREE launches whatever their number (libmdct_jpegenc_batch.so, include/mdct_jpegenc_batch.h; DESIGN.md
+    section 4.15): the front kernel over the tiles of all images, the scan coder with one workgroup per MCU row of the batch, the
+    packer likewise.  The host images go up in one copy (device images are not copied); planes, segments, counts, row offsets and
+    output are one allocation each; the row offsets come back in one copy, the scans' bytes in one more.  The output's first capacity
+    is the sum of the images' first capacities; if the scans do not fit, only the packing launch runs again, into the worst case.  A
+    batch of more than 16384 MCU rows is cut into consecutive groups below that bound, three launches each.  A grey image has no
+    interleaved form: it is coded by encode_jpeg inside the call, on the same stream, at its place in the list.
+
+    stream: as for encode_jpeg -- every launch, allocation, upload and copy back of the call is ordered on it."""
+    import torch
+
+    if isinstance(images, (np.ndarray, torch.Tensor)):
+        if len(images.shape) != 4:
+            raise ValueError(f"images of shape {list(images.shape)}: a sequence of images, or one 4-D array or tensor of them")
+        images = [images[i] for i in range(images.shape[0])]
+    images = list(images)
+    try:  # what encode_jpeg checks first, for the first image
+        q = _quality(quality)
+        if layout not in _LAYOUTS:
+            raise ValueError(f"layout {layout!r} ('HWC' or 'CHW')")
+        sampling = sampling_of(subsampling)
+    except ValueError as e:
+        if images:
+            e.file = 0
+        raise
+    if not images:
+        return []
+    # ---- host: every image's arguments
+    shapes, dev = [], None
+    for i, image in enumerate(images):
+        try:
+            if isinstance(image, np.ndarray):
+                if image.dtype != np.uint8:
+                    raise ValueError(f"image dtype {image.dtype}: uint8")
+            elif not isinstance(image, torch.Tensor) or image.dtype != torch.uint8:
+                raise ValueError("image: a uint8 numpy array or torch tensor")
+            H, W, grey = _image_shape(image, layout)
+            place = None
+            if not grey and isinstance(image, torch.Tensor) and image.is_cuda:
+                place = _input_of(image, layout)
+                if dev is not None and image.device != dev:
+                    raise ValueError(f"image on {image.device}: the device images of one batch lie on one device ({dev})")
+                dev = image.device
+            shapes.append((H, W, grey, place))
+        except ValueError as e:
+            e.file = i
+            raise
+    if device is not None:
+        dev = torch.device(f"cuda:{device}" if isinstance(device, int) else device) if dev is None else dev
+    elif dev is None:
+        dev = torch.device("cuda")
+    luma, chroma = quality_tables(q)
+    results = [None] * len(images)
+    colour = [i for i, (_, _, grey, _) in enumerate(shapes) if not grey]
+    with torch.cuda.device(dev), api._on_stream(stream, dev):
+        # ---- the host images of the colour path: one buffer, one copy
+        at, n_up = {}, 0
+        for i in colour:
+            H, W, _, place = shapes[i]
+            if place is None:
+                at[i] = n_up
+                n_up += _align(3 * W * H)
+        if n_up:
+            staging = np.empty(n_up, dtype=np.uint8)
+            for i, a0 in at.items():
+                H, W = shapes[i][:2]
+                src = images[i] if isinstance(images[i], np.ndarray) else images[i].numpy()
+                staging[a0:a0 + 3 * W * H] = np.ascontiguousarray(src).reshape(-1)
+            uploaded = torch.from_numpy(staging).to(dev)
+        # ---- consecutive groups of colour images within the packer's row bound
+        groups, rows = [[]], 0
+        for i in colour:
+            my = mcu_grid(shapes[i][1], shapes[i][0], sampling)[1]
+            if groups[-1] and rows + my > _jpegenc_batch_lib.MAX_ROWS:
+                groups.append([])
+                rows = 0
+            groups[-1].append(i)
+            rows += my
+        for group in groups:
+            if group:
+                inputs = []
+                for i in group:
+                    H, W, _, place = shapes[i]
+                    if place is None:
+                        inputs.append((uploaded.data_ptr() + at[i], 3 * W if layout == "HWC" else W, W * H))
+                    else:
+                        inputs.append((images[i].data_ptr(),) + place)
+                _encode_group(torch, group, inputs, shapes, sampling, layout, (luma, chroma), dev, stream, results)
+        for i, (_, _, grey, _) in enumerate(shapes):
+            if grey:
+                results[i] = encode_jpeg(images[i], q, subsampling, layout, device=dev, stream=stream)
+    return results
+
+
+def _encode_group(torch, group, inputs, shapes, sampling, layout, tabs, dev, stream, results):
+    """the three launches of encode_jpeg_batch for the colour images `group` names (inputs: (address, pitch, plane stride) of each on
+    the device); their files go to results"""
+    with api._on_stream(stream, dev):  # (the caller's, again: every allocation and copy below is on the stream of the launches)
+        grids, n_planes, n_seg, capacity, worst = [], 0, 0, 0, 0
+        for i in group:
+            H, W = shapes[i][:2]
+            mcus_x, mcus_y, sizes = mcu_grid(W, H, sampling)
+            stride = scan_seg_stride(mcus_x, sampling)
+            p_at = []
+            for pw, ph in sizes:
+                p_at.append(n_planes)
+                n_planes += _align(pw * ph)
+            grids.append((mcus_x, mcus_y, sizes, stride, p_at, n_seg))
+            n_seg += _align(mcus_y * stride)
+            capacity += _first_capacity(sum(pw * ph for pw, ph in sizes))
+            worst += 2 * mcus_y * stride
+        planes = torch.empty((n_planes,), dtype=torch.uint8, device=dev)
+        seg = torch.empty((n_seg,), dtype=torch.uint8, device=dev)
+        described = []
+        for i, (address, pitch, pstride), (mcus_x, mcus_y, sizes, stride, p_at, s_at) in zip(group, inputs, grids):
+            H, W = shapes[i][:2]
+            described.append((address, pitch, pstride, W, H, [(planes.data_ptr() + a0, pw, pw, ph, h, v) for a0, (pw, ph), (h, v) in zip(p_at, sizes, sampling)],
+                              seg.data_ptr() + s_at, stride))
+        plan = BatchPlan(described, layout, tabs)
+        try:
+            counts = torch.empty((2, plan.n_rows), dtype=torch.int32, device=dev)
+            off = torch.empty((plan.n_rows + 1,), dtype=torch.int64, device=dev)
+            out = torch.empty((capacity,), dtype=torch.uint8, device=dev)
+            image = torch.empty((plan.image_bytes,), dtype=torch.uint8, device=dev)  # the caching allocator's blocks are 512-byte aligned
+            image.copy_(torch.from_numpy(plan.bind(image, counts[0], counts[1])))
+            plan.planes(stream)
+            plan.scan(stream)
+            plan.pack(out, off, stream)
+            offsets = off.cpu().numpy()  # the one copy that waits for the scans: it is ordered on the call's stream
+            if int(offsets[-1]) > out.numel():  # the segments are there: only the packing runs again, into the worst case
+                out = torch.empty((worst,), dtype=torch.uint8, device=dev)
+                plan.pack(out, off, stream)
+                offsets = off.cpu().numpy()
+            first = plan.first_row
+        finally:
+            plan.close()
+        scans = out[:int(offsets[-1])].cpu().numpy()
+        luma, chroma = tabs
+        for k, (i, (mcus_x, _, _, _, _, _)) in enumerate(zip(group, grids)):
+            H, W = shapes[i][:2]
+            scan = scans[int(offsets[first[k]]):int(offsets[first[k + 1]])]
+            results[i] = jfif.write_jpeg([dict(qtable=luma), dict(qtable=chroma), dict(qtable=chroma)], W, H, specs=None, sampling=sampling,
+                                         interleaved=dict(scan=scan, mcus_per_row=mcus_x))
