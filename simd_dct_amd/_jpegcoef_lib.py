@@ -5,13 +5,9 @@ Its own signature table: a separate library, linked against libmdct_hip.so and l
 object is missing or fails to load, every entry point raises.
 """
 import ctypes
-import os
 
 from . import _jpegenc_opt_lib, _lib
 from ._jpegenc_opt_lib import HIST_CLASS, Spec  # mdct_jpegenc_opt_spec  # noqa: F401
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmdct_jpegcoef.so")
 
 c_size_t = ctypes.c_size_t
 c_void_p = ctypes.c_void_p
@@ -38,14 +34,5 @@ SIGNATURES = {
     "mdct_jpegcoef_last_error": (ctypes.c_char_p, []),
 }
 
-_lib_handle = None
-
-
-def load():
-    """Load libmdct_jpegcoef.so (once), after libmdct_hip.so and libmdct_jpegenc_opt.so (which it links against)."""
-    global _lib_handle
-    if _lib_handle is None:
-        _lib.load()
-        _jpegenc_opt_lib.load()
-        _lib_handle = _lib.bind(LIB_PATH, SIGNATURES)
-    return _lib_handle
+LIB = _lib.Library("mdct_jpegcoef", ("mdct_jpegcoef.h",), SIGNATURES, after=(_jpegenc_opt_lib.LIB,))
+load, LIB_PATH = LIB.load, LIB.path

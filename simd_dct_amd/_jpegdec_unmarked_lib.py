@@ -5,12 +5,8 @@ Its own signature table: a separate library, linked against libmdct_jpegdec.so (
 libmdct_hip.so.  No fallback: if the shared object is missing or fails to load, every entry point raises.
 """
 import ctypes
-import os
 
 from . import _jpegdec_lib, _lib
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmdct_jpegdec_unmarked.so")
 
 c_size_t = ctypes.c_size_t
 c_void_p = ctypes.c_void_p
@@ -28,13 +24,5 @@ SIGNATURES = {
     "mdct_jpegdec_unmarked_last_error": (ctypes.c_char_p, []),
 }
 
-_lib_handle = None
-
-
-def load():
-    """Load libmdct_jpegdec_unmarked.so (once), after libmdct_jpegdec.so and libmdct_hip.so."""
-    global _lib_handle
-    if _lib_handle is None:
-        _jpegdec_lib.load()
-        _lib_handle = _lib.bind(LIB_PATH, SIGNATURES)
-    return _lib_handle
+LIB = _lib.Library("mdct_jpegdec_unmarked", ("mdct_jpegdec_unmarked.h",), SIGNATURES, after=(_jpegdec_lib.LIB,), label="mdct_jpegdec")
+load, LIB_PATH = LIB.load, LIB.path

@@ -5,12 +5,8 @@ Its own signature table: a separate library, linked against libmdct_hip.so.  No 
 to load, every entry point raises.
 """
 import ctypes
-import os
 
 from . import _jpegenc_lib, _lib
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmdct_jpegenc_batch.so")
 
 c_size_t = ctypes.c_size_t
 c_void_p = ctypes.c_void_p
@@ -50,13 +46,5 @@ SIGNATURES = {
     "mdct_jpegenc_batch_last_error": (ctypes.c_char_p, []),
 }
 
-_lib_handle = None
-
-
-def load():
-    """Load libmdct_jpegenc_batch.so (once), after libmdct_hip.so (whose launch tally, Huffman specifications and HIP runtime it shares)."""
-    global _lib_handle
-    if _lib_handle is None:
-        _lib.load()
-        _lib_handle = _lib.bind(LIB_PATH, SIGNATURES)
-    return _lib_handle
+LIB = _lib.Library("mdct_jpegenc_batch", ("mdct_jpegenc_batch.h",), SIGNATURES)
+load, LIB_PATH = LIB.load, LIB.path

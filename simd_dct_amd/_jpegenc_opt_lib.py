@@ -5,13 +5,10 @@ Its own signature table: a separate library, linked against libmdct_hip.so.  No 
 load, every entry point raises.
 """
 import ctypes
-import os
 
 from . import _lib
 from ._jpegenc_scan_lib import Plane  # mdct_jpegenc_scan_plane  # noqa: F401
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmdct_jpegenc_opt.so")
 HIST_CLASS = 272  # MDCT_JPEGENC_OPT_HIST_CLASS
 
 c_size_t = ctypes.c_size_t
@@ -37,13 +34,5 @@ SIGNATURES = {
     "mdct_jpegenc_opt_last_error": (ctypes.c_char_p, []),
 }
 
-_lib_handle = None
-
-
-def load():
-    """Load libmdct_jpegenc_opt.so (once), after libmdct_hip.so (whose launch tally and HIP runtime it shares)."""
-    global _lib_handle
-    if _lib_handle is None:
-        _lib.load()
-        _lib_handle = _lib.bind(LIB_PATH, SIGNATURES)
-    return _lib_handle
+LIB = _lib.Library("mdct_jpegenc_opt", ("mdct_jpegenc_opt.h",), SIGNATURES)
+load, LIB_PATH = LIB.load, LIB.path

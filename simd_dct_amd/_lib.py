@@ -2,8 +2,13 @@
 
 The HIP library is the product.  There is NO fallback: if the shared object is missing
 or fails to load, every entry point raises.
+
+Also the one loader of all the engine's libraries: Library, which every binding module (_*_lib.py) ends in, and the registry
+LIBRARIES / load_all().  A new library is a row of the Makefile's table and a binding module.
 """
 import ctypes
+import glob
+import importlib
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -140,6 +145,10 @@ MANGLED = (
 _lib = None
 
 
+class MdctError(RuntimeError):
+    pass
+
+
 def bind(path, signatures, hint=""):
     """Load the shared object at `path` and declare restype / argtypes of every function in `signatures`."""
     if not os.path.exists(path):
@@ -165,3 +174,69 @@ def load():
             pass
     _lib = bind(LIB_PATH, SIGNATURES, "  simd_dct_amd has no CPU fallback.")
     return _lib
+
+
+_registered = []  # every Library made so far, in that order: the libraries one names in `after` exist before it does
+
+
+class Library:
+    """One shared library of the engine, lib<name>.so beside this file: `headers` (in include/) declare it, `signatures` bind it, it
+    links against libmdct_hip.so and the libraries `after` (the Makefile's row of it says the same), and its errors are reported under
+    `label` (default: its name).  No fallback: if the shared object is missing or fails to load, every entry point raises."""
+
+    def __init__(self, name, headers, signatures, after=(), label=None):
+        self.name, self.headers, self.signatures, self.after, self.label = name, tuple(headers), signatures, tuple(after), label or name
+        self._last_error = next(n for n in signatures if n.endswith("_last_error"))
+        self._handle = None
+        _registered.append(self)
+
+    @property
+    def path(self):
+        return os.path.join(_HERE, "lib" + self.name + ".so")
+
+    def load(self):
+        """Load the library (once), after libmdct_hip.so (whose launch tally and HIP runtime it shares) and those it links against."""
+        if self._handle is None:
+            load()
+            for lib in self.after:
+                lib.load()
+            self._handle = bind(self.path, self.signatures)
+        return self._handle
+
+    def last_error(self):
+        return getattr(self.load(), self._last_error)().decode()
+
+    def error(self, rc):
+        return MdctError(f"{self.label} status {rc}: {self.last_error()}")
+
+    def check(self, rc):
+        if rc != 0:
+            raise self.error(rc)
+
+
+class _Core(Library):
+    """libmdct_hip.so itself: LIB_PATH and load() above are its path and its loader"""
+
+    path = property(lambda self: LIB_PATH)
+
+    def load(self):
+        return load()
+
+
+LIB = _Core("mdct_hip", ("mdct.h", "simd_dct_shim.h"), SIGNATURES, label="mdct")
+
+
+def __getattr__(name):
+    """LIBRARIES: all the libraries, in dependency order.  Every binding module (_*_lib.py beside this file) ends in its Library;
+    importing them here, at first use, registers the ones no wrapper has imported yet and loads no shared object."""
+    if name != "LIBRARIES":
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    for f in sorted(glob.glob(os.path.join(_HERE, "_*_lib.py"))):
+        importlib.import_module("." + os.path.basename(f)[:-3], __package__)
+    return list(_registered)
+
+
+def load_all():
+    """Load every library; a missing one is an error."""
+    for lib in __getattr__("LIBRARIES"):
+        lib.load()

@@ -29,24 +29,27 @@ QUANTIZE_BASE = np.array(
     dtype=np.float32)
 
 
-class MdctError(RuntimeError):
-    pass
+MdctError = _lib.MdctError
+last_error, _check = _lib.LIB.last_error, _lib.LIB.check
 
 
-def last_error():
-    return _lib.load().mdct_last_error().decode()
-
-
-def _check(rc):
-    if rc != 0:
-        raise MdctError(f"mdct status {rc}: {last_error()}")
+def _lut64(t):
+    """a table of 64 numbers as contiguous float32"""
+    return np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64))
 
 
 def _lut_ptr(lut):
     if lut is None:
         return None, None
-    a = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(64))
+    a = _lut64(lut)
     return a, a.ctypes.data_as(_lib.f32p)
+
+
+def _device(device):
+    """None, a device index, a string or a torch.device -> the torch.device"""
+    import torch
+
+    return torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
 
 
 def _ptr(t):

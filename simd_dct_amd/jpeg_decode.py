@@ -36,13 +36,7 @@ class JpegDecodeError(RuntimeError):
 STATUS_NAMES = _jpegdec_prog_lib.STATUS_NAMES  # every interval status a restart-marked or progressive scan can end in
 
 
-def last_error():
-    return _jpegdec_lib.load().mdct_jpegdec_last_error().decode()
-
-
-def _check(rc):
-    if rc != 0:
-        raise api.MdctError(f"mdct_jpegdec status {rc}: {last_error()}")
+last_error, _check = _jpegdec_lib.LIB.last_error, _jpegdec_lib.LIB.check
 
 
 def _spec_arrays(specs):
@@ -120,8 +114,7 @@ def decode(desc, tables, scan, offsets, status, scan_len=None, stream=None):
     _check(_jpegdec_lib.load().mdct_jpegdec_decode(ctypes.byref(desc), tables.handle, _ptr(scan), L, _ptr(offsets), _ptr(status), _stream(stream)))
 
 
-def unmarked_last_error():
-    return _jpegdec_unmarked_lib.load().mdct_jpegdec_unmarked_last_error().decode()
+unmarked_last_error = _jpegdec_unmarked_lib.LIB.last_error
 
 
 def unmarked_workspace(desc, scan_len):
@@ -135,12 +128,10 @@ def decode_unmarked(desc, tables, scan, workspace, status, scan_len=None, sync_r
     rc = _jpegdec_unmarked_lib.load().mdct_jpegdec_decode_unmarked(ctypes.byref(desc), tables.handle, _ptr(scan), L, _ptr(workspace),
                                                                    workspace.numel() * workspace.element_size(), _ptr(status),
                                                                    sync_rounds, _stream(stream))
-    if rc != 0:
-        raise api.MdctError(f"mdct_jpegdec status {rc}: {unmarked_last_error()}")
+    _jpegdec_unmarked_lib.LIB.check(rc)  # (reported under the label mdct_jpegdec)
 
 
-def prog_last_error():
-    return _jpegdec_prog_lib.load().mdct_jpegdec_prog_last_error().decode()
+prog_last_error = _jpegdec_prog_lib.LIB.last_error
 
 
 def prog_intervals(desc, ss, se):
@@ -154,10 +145,8 @@ def prog_intervals(desc, ss, se):
 def decode_prog(desc, ss, se, tables, scan, offsets, status, scan_len=None, stream=None):
     """mdct_jpegdec_prog_decode: one scan of a progressive file, band ss..se; offsets as index() leaves them"""
     L = scan.numel() if scan_len is None else scan_len
-    rc = _jpegdec_prog_lib.load().mdct_jpegdec_prog_decode(ctypes.byref(desc), ss, se, tables.handle, _ptr(scan), L, _ptr(offsets), _ptr(status),
-                                                           _stream(stream))
-    if rc != 0:
-        raise api.MdctError(f"mdct_jpegdec_prog status {rc}: {prog_last_error()}")
+    _jpegdec_prog_lib.LIB.check(_jpegdec_prog_lib.load().mdct_jpegdec_prog_decode(ctypes.byref(desc), ss, se, tables.handle, _ptr(scan), L, _ptr(offsets),
+                                                                                  _ptr(status), _stream(stream)))
 
 
 def read_file(data):
@@ -257,7 +246,7 @@ def scaled_geometry(info, scale_denom):
 def scaled_last_error():
     from . import _jpegscale_lib
 
-    return _jpegscale_lib.load().mdct_jpegscale_last_error().decode()
+    return _jpegscale_lib.LIB.last_error()
 
 
 def scaled_inverse(planes, level_shift=True, stream=None):
@@ -275,12 +264,10 @@ def scaled_inverse(planes, level_shift=True, stream=None):
         if px.dim() != 2 or coef.dim() != 2 or px.stride(1) != 1 or coef.stride(1) != 1:
             raise ValueError(f"plane {k}: [rows, columns] tensors with contiguous columns")
         if lut is not None:
-            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(64))
+            lut = api._lut64(lut)
             keep.append(lut)
         arr[k] = _jpegscale_lib.Plane(_ptr(coef), coef.stride(0), _ptr(px), px.stride(0), bx, by, None if lut is None else lut.ctypes.data, n, rx, ry)
-    rc = lib.mdct_jpegscale_inv_i16_u8(arr, len(planes), int(bool(level_shift)), _stream(stream))
-    if rc != 0:
-        raise api.MdctError(f"mdct_jpegscale status {rc}: {scaled_last_error()}")
+    _jpegscale_lib.LIB.check(lib.mdct_jpegscale_inv_i16_u8(arr, len(planes), int(bool(level_shift)), _stream(stream)))
 
 
 def colour_sampling(info, scale_denom):
@@ -334,7 +321,7 @@ def decode_coefficients(data, device=None, stream=None, *, info=None):
 
     if info is None:
         info = read_file(data)
-    dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+    dev = api._device(device)
     raw = bytes(data)
     geo, grid = geometry(info)
     # zeroed: a non-interleaved scan of a subsampled component covers its own block grid (T.81 A.2.2), which may be smaller than the
@@ -381,7 +368,7 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
     info = read_file(data)
     if mode == "RGB":
         _colour_params(info)
-    dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+    dev = api._device(device)
     geo, _ = geometry(info)
     _, coefs = decode_coefficients(data, dev, stream, info=info)
     with torch.cuda.device(dev), api._on_stream(stream, dev):
@@ -401,8 +388,7 @@ def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None
     return (out, coefs) if coefficients else out
 
 
-def batch_last_error():
-    return _jpegdec_batch_lib.load().mdct_jpegdec_batch_last_error().decode()
+batch_last_error = _jpegdec_batch_lib.LIB.last_error
 
 
 class BatchPlan:
@@ -424,7 +410,7 @@ class BatchPlan:
         h, bad = ctypes.c_void_p(), ctypes.c_size_t()
         rc = lib.mdct_jpegdec_batch_plan_create(ctypes.byref(h), arr, len(scans), total_bytes, ctypes.byref(bad))
         if rc != 0:
-            e = api.MdctError(f"mdct_jpegdec_batch status {rc}: {batch_last_error()}")
+            e = _jpegdec_batch_lib.LIB.error(rc)
             e.scan = bad.value if bad.value < len(scans) else None
             raise e
         self.handle, self._lib = h, lib
@@ -455,9 +441,7 @@ class BatchPlan:
         """the chunk table: the scan every index chunk of the batch belongs to"""
         return [int(self._lib.mdct_jpegdec_batch_chunk_scan(self.handle, c)) for c in range(self.n_chunks)]
 
-    def _rc(self, rc):
-        if rc != 0:
-            raise api.MdctError(f"mdct_jpegdec_batch status {rc}: {batch_last_error()}")
+    _rc = staticmethod(_jpegdec_batch_lib.LIB.check)
 
     def bind(self, device_image, scan_bytes, offsets, status):
         """mdct_jpegdec_batch_bind: -> the image as a numpy uint8 array, to be copied to device_image (a device tensor of image_bytes
@@ -559,7 +543,7 @@ def decode_jpeg_batch(files, device=None, stream=None, *, mode=None, layout="HWC
     if jobs or singles:
         import torch
 
-        dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+        dev = api._device(device)
     # ---- files outside the batch path, one at a time
     for i in singles:
         try:
@@ -651,8 +635,7 @@ def _colour_params(info):
         raise jfif.JpegFormatError("fractional sampling ratio: " + ", ".join(f"{c['h']}x{c['v']}" for c in comps))
 
 
-def colour_last_error():
-    return _jpegcolor_lib.load().mdct_jpegcolor_last_error().decode()
+colour_last_error = _jpegcolor_lib.LIB.last_error
 
 
 def to_rgb(planes, sampling, width, height, colour="YCbCr", layout="HWC", out=None, stream=None):
@@ -679,10 +662,8 @@ def to_rgb(planes, sampling, width, height, colour="YCbCr", layout="HWC", out=No
     if out.dtype != torch.uint8 or tuple(out.shape) != shape or out.stride(-1) != 1 or (layout == "HWC" and out.stride(1) != 3):
         raise ValueError(f"out: uint8 {list(shape)} with contiguous {'pixels' if layout == 'HWC' else 'rows'}")
     pitch, stride = (out.stride(0), 0) if layout == "HWC" else (out.stride(1), out.stride(0))
-    rc = _jpegcolor_lib.load().mdct_jpegcolor_to_rgb(arr, len(planes), width, height, _COLOURS[colour], _LAYOUTS[layout], out.data_ptr(),
-                                                     pitch, stride, _stream(stream))
-    if rc != 0:
-        raise api.MdctError(f"mdct_jpegcolor status {rc}: {colour_last_error()}")
+    _jpegcolor_lib.LIB.check(_jpegcolor_lib.load().mdct_jpegcolor_to_rgb(arr, len(planes), width, height, _COLOURS[colour], _LAYOUTS[layout], out.data_ptr(),
+                                                                         pitch, stride, _stream(stream)))
     return out
 
 

@@ -76,8 +76,7 @@ def mcu_grid(width, height, sampling):
     return mx, my, [(mx * 8 * h, my * 8 * v) for h, v in sampling]
 
 
-def last_error():
-    return _jpegenc_lib.load().mdct_jpegenc_last_error().decode()
+last_error = _jpegenc_lib.LIB.last_error
 
 
 def _image_shape(image, layout):
@@ -135,10 +134,8 @@ def to_planes(image, subsampling="4:2:0", layout="HWC", planes=None, stream=None
             raise ValueError(f"plane {k}: uint8 device tensor [rows, columns] with contiguous columns")
         arr[k] = _jpegenc_lib.Plane(p.data_ptr(), p.stride(0), p.shape[1], p.shape[0], h, v)
     colour = _jpegenc_lib.GREY if grey else _jpegenc_lib.RGB
-    rc = _jpegenc_lib.load().mdct_jpegenc_from_rgb(image.data_ptr(), pitch, stride, W, H, colour, _LAYOUTS[layout], arr, len(planes),
-                                                   _stream(stream))
-    if rc != 0:
-        raise api.MdctError(f"mdct_jpegenc status {rc}: {last_error()}")
+    _jpegenc_lib.LIB.check(_jpegenc_lib.load().mdct_jpegenc_from_rgb(image.data_ptr(), pitch, stride, W, H, colour, _LAYOUTS[layout], arr, len(planes),
+                                                                     _stream(stream)))
     return planes
 
 
@@ -162,21 +159,19 @@ def scan_rows(planes, sampling, luts, out, seg_bytes, ff_counts, seg_stride=None
     one segment per MCU row seg_stride apart (default: scan_seg_stride); seg_bytes / ff_counts: int32 per MCU row.  MCU rows my0 .. my1
     (default: all) are coded.  Returns the status (raises unless check=False)."""
     arr = _plane_array(planes, sampling)
-    tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+    tabs = [api._lut64(t) for t in luts]
     mcus_x, mcus_y = planes[-1].shape[1] // 8, planes[-1].shape[0] // 8
     if seg_stride is None:
         seg_stride = scan_seg_stride(mcus_x, sampling)
     lib = _jpegenc_scan_lib.load()
     rc = lib.mdct_jpegenc_scan_rows(arr, len(planes), tabs[0].ctypes.data, tabs[1].ctypes.data, my0, mcus_y if my1 is None else my1, out.data_ptr(), seg_stride,
                                     seg_bytes.data_ptr(), ff_counts.data_ptr(), _stream(stream))
-    if check and rc != 0:
-        raise api.MdctError(f"mdct_jpegenc_scan status {rc}: {lib.mdct_jpegenc_scan_last_error().decode()}")
+    if check:
+        _jpegenc_scan_lib.LIB.check(rc)
     return rc
 
 
-def _opt_error(rc):
-    lib = _jpegenc_opt_lib.load()
-    return api.MdctError(f"mdct_jpegenc_opt status {rc}: {lib.mdct_jpegenc_opt_last_error().decode()}")
+_opt_error = _jpegenc_opt_lib.LIB.error
 
 
 def symbol_histogram(planes, sampling, luts, interleaved=False, hist=None, stream=None, check=True):
@@ -191,7 +186,7 @@ def symbol_histogram(planes, sampling, luts, interleaved=False, hist=None, strea
     if not isinstance(interleaved, (bool, np.bool_)):
         raise ValueError(f"interleaved {interleaved!r}: a bool")
     arr = _plane_array(planes, sampling)
-    tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+    tabs = [api._lut64(t) for t in luts]
     if hist is None:
         with api._on_stream(stream, planes[0].device):
             hist = torch.empty((2, _jpegenc_opt_lib.HIST_CLASS), dtype=torch.int32, device=planes[0].device)
@@ -255,7 +250,7 @@ def opt_rows(plane, lut, specs, out, seg_bytes, ff_counts, uncoded, seg_stride=N
     if plane.dim() != 2 or plane.stride(1) != 1 or plane.element_size() != 1:
         raise ValueError("plane: uint8 tensor [rows, columns] with contiguous columns")
     sp = _Specs({0: specs[0], 1: specs[1]}, (0, 1))
-    tab = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(64))
+    tab = api._lut64(lut)
     ph, pw = plane.shape
     if seg_stride is None:
         seg_stride = opt_seg_stride(pw // 8)
@@ -271,7 +266,7 @@ def opt_scan_rows(planes, sampling, luts, specs, out, seg_bytes, ff_counts, unco
     the Annex K tables, seg_stride at least opt_seg_stride(blocks per MCU row), and uncoded as for opt_rows."""
     arr = _plane_array(planes, sampling)
     sp = _Specs(specs, (0, 1, 2, 3))
-    tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+    tabs = [api._lut64(t) for t in luts]
     mcus_x, mcus_y = planes[-1].shape[1] // 8, planes[-1].shape[0] // 8
     if seg_stride is None:
         seg_stride = opt_seg_stride(mcus_x * sum(h * v for h, v in sampling))
@@ -398,7 +393,7 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     sampling = sampling_of(subsampling, grey)
     sizes = component_sizes(W, H, sampling)
     luma, chroma = quality_tables(q)
-    dev = torch.device("cuda" if device is None else (f"cuda:{device}" if isinstance(device, int) else device))
+    dev = api._device(device)
     if isinstance(image, np.ndarray):
         image = torch.from_numpy(np.ascontiguousarray(image))
     if not image.is_cuda:
@@ -449,8 +444,7 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     return jfif.write_jpeg(comps, W, H, specs=specs, sampling=sampling)
 
 
-def batch_last_error():
-    return _jpegenc_batch_lib.load().mdct_jpegenc_batch_last_error().decode()
+batch_last_error = _jpegenc_batch_lib.LIB.last_error
 
 
 class BatchPlan:
@@ -468,11 +462,11 @@ class BatchPlan:
             for k, p in enumerate(planes):
                 arr[i].planes[k] = _jpegenc_lib.Plane(*p)
             arr[i].seg, arr[i].seg_stride = seg, seg_stride
-        tabs = [np.ascontiguousarray(np.asarray(t, dtype=np.float32).reshape(64)) for t in luts]
+        tabs = [api._lut64(t) for t in luts]
         h, bad = ctypes.c_void_p(), ctypes.c_size_t()
         rc = lib.mdct_jpegenc_batch_plan_create(ctypes.byref(h), arr, len(images), _LAYOUTS[layout], tabs[0].ctypes.data, tabs[1].ctypes.data, ctypes.byref(bad))
         if rc != 0:
-            e = api.MdctError(f"mdct_jpegenc_batch status {rc}: {batch_last_error()}")
+            e = _jpegenc_batch_lib.LIB.error(rc)
             e.image = bad.value if bad.value < len(images) else None
             raise e
         self.handle, self._lib = h, lib
@@ -489,9 +483,7 @@ class BatchPlan:
         return [(int(lib.mdct_jpegenc_batch_row_image(h, r)), int(lib.mdct_jpegenc_batch_row_last(h, r)), int(lib.mdct_jpegenc_batch_row_marker(h, r)))
                 for r in range(self.n_rows)]
 
-    def _rc(self, rc):
-        if rc != 0:
-            raise api.MdctError(f"mdct_jpegenc_batch status {rc}: {batch_last_error()}")
+    _rc = staticmethod(_jpegenc_batch_lib.LIB.check)
 
     def bind(self, device_image, seg_bytes, ff_counts):
         """mdct_jpegenc_batch_bind: -> the image as a numpy uint8 array, to be copied to device_image (a device tensor of image_bytes

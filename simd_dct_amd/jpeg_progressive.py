@@ -18,12 +18,7 @@ HIST_CLASS, AC_HIST = _jpegprog_lib.HIST_CLASS, _jpegprog_lib.AC_HIST
 LUMA_BANDS, CHROMA_BANDS = ((1, 2), (3, 9), (10, 63)), ((1, 63),)
 
 
-def last_error():
-    return _jpegprog_lib.load().mdct_jpegprog_last_error().decode()
-
-
-def _error(rc):
-    return api.MdctError(f"mdct_jpegprog status {rc}: {last_error()}")
+last_error, _error = _jpegprog_lib.LIB.last_error, _jpegprog_lib.LIB.error
 
 
 def check_bands(bands, nc):

@@ -19,12 +19,7 @@ MIRRORED = {"flip_h": "x", "flip_v": "y", "rot180": "xy", "transverse": "xy", "r
 INTERLEAVED_LUMA = ((2, 2), (2, 1), (1, 1))
 
 
-def last_error():
-    return _jpegcoef_lib.load().mdct_jpegcoef_last_error().decode()
-
-
-def _error(rc):
-    return api.MdctError(f"mdct_jpegcoef status {rc}: {last_error()}")
+last_error, _error = _jpegcoef_lib.LIB.last_error, _jpegcoef_lib.LIB.error
 
 
 def _plane(t, blocks_x=None, blocks_y=None, h=1, v=1, name="plane"):

@@ -3,7 +3,6 @@
 reference's status codes before touching any device."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,22 +17,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def lib():
     G.build_hip()
     return _lib.load()
-
-
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mdct_[a-z0-9_]+)\s*\(", txt)))
-
-
-def test_every_declared_symbol_is_exported_and_bound(lib):
-    names = _declared("mdct.h") + _declared("simd_dct_shim.h")
-    assert len(names) >= 20
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/ but not exported"
-        assert n in _lib.SIGNATURES, f"{n} has no ctypes signature"
-    for n in _lib.SIGNATURES:
-        assert n in names, f"{n} bound but not declared in include/"
 
 
 def test_reference_cxx_symbols_exported(lib):

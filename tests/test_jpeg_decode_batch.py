@@ -231,23 +231,6 @@ def test_equal_table_specifications_share_one_set():
     assert q.table_set == [0, 1]
 
 
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mdct_[a-z0-9_]+)\s*\(", txt)))
-
-
-def test_every_declared_symbol_is_exported_and_bound():
-    names = _declared("mdct_jpegdec_batch.h")
-    assert len(names) >= 10 and all(n.startswith("mdct_jpegdec_batch_") for n in names)
-    lib = _jpegdec_batch_lib.load()
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/ but not exported"
-        assert n in _jpegdec_batch_lib.SIGNATURES, f"{n} has no ctypes signature"
-    for n in _jpegdec_batch_lib.SIGNATURES:
-        assert n in names, f"{n} bound but not declared in include/"
-
-
 def test_code_object_holds_the_four_kernels():
     from test_kernel_coverage import code_object_kernels
     assert code_object_kernels(lib=_jpegdec_batch_lib.LIB_PATH)[0] == BATCH_KERNELS

@@ -12,11 +12,9 @@ GPU: the mixed batch (the shapes are listed at images()) at every subsampling an
 tensor; the launch count, which does not depend on the number of images; grey images at their place; the second packing pass; the
 three entry points driven directly over buffers with canaries, against scan_rows + jpeg_pack_rows on each image alone; a call on a
 stream that is not the current one, behind a stall."""
-import ctypes
 import functools
 import io
 import os
-import re
 
 import numpy as np
 import pytest
@@ -147,28 +145,6 @@ def test_plan_refuses_two_subsamplings_in_one_batch():
     with pytest.raises(api.MdctError, match="one subsampling per batch") as e:
         J.BatchPlan([described(0, 16, 16), described(1, 16, 16, "4:2:2")], "HWC", J.quality_tables(75))
     assert e.value.image == 1
-
-
-def _declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(mdct_[a-z0-9_]+)\s*\(", txt)))
-
-
-def test_every_declared_symbol_is_exported_and_bound():
-    names = _declared("mdct_jpegenc_batch.h")
-    assert len(names) >= 10 and all(n.startswith("mdct_jpegenc_batch_") for n in names)
-    lib = _jpegenc_batch_lib.load()
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/ but not exported"
-        assert n in _jpegenc_batch_lib.SIGNATURES, f"{n} has no ctypes signature"
-    for n in _jpegenc_batch_lib.SIGNATURES:
-        assert n in names, f"{n} bound but not declared in include/"
-    exported = ctypes.CDLL(_jpegenc_batch_lib.LIB_PATH)
-    for n in names:
-        assert getattr(exported, n)
-    src = open(os.path.join(ROOT, "include", "mdct_jpegenc_batch.h")).read()
-    assert f"#define MDCT_JPEGENC_BATCH_MAX_ROWS {_jpegenc_batch_lib.MAX_ROWS}\n" in src
 
 
 def test_code_object_holds_the_ten_kernels():
