@@ -13,11 +13,11 @@
  *
  * Scans without restart markers (restart_interval 0, refused here) are decoded by libmdct_jpegdec_unmarked.so
  * (include/mdct_jpegdec_unmarked.h), with the same table handle and descriptor.
- * The scans of a progressive file (spectral selection only, with restart markers) are decoded by libmdct_jpegdec_prog.so
+ * The scans of a progressive file (spectral selection and successive approximation) are decoded by libmdct_jpegdec_prog.so
  * (include/mdct_jpegdec_prog.h), with the same table handle, descriptor and index.
  * The restart-marked scans of many files at once, in four launches for the whole batch: libmdct_jpegdec_batch.so
  * (include/mdct_jpegdec_batch.h), with the same descriptor, checks and per-interval decoder.
- * Out of scope: successive approximation / arithmetic / 12-bit / lossless JPEG.  Chroma upsampling and colour conversion: include/mdct_jpegcolor.h. */
+ * Out of scope: arithmetic / 12-bit / lossless JPEG.  Chroma upsampling and colour conversion: include/mdct_jpegcolor.h. */
 #ifndef MDCT_JPEGDEC_H
 #define MDCT_JPEGDEC_H
 

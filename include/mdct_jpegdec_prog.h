@@ -1,7 +1,8 @@
-/* mdct_jpegdec_prog.h -- C-ABI of libmdct_jpegdec_prog.so: the scans of a progressive JPEG (SOF2) with spectral selection only
- * (ITU-T T.81 Annex G, Ah = Al = 0) and restart markers -> quantised int16 coefficient planes on the GPU.
+/* mdct_jpegdec_prog.h -- C-ABI of libmdct_jpegdec_prog.so: the scans of a progressive JPEG (SOF2; ITU-T T.81 Annex G: spectral
+ * selection, and successive approximation through mdct_jpegdec_prog_decode_approx) -> quantised int16 coefficient planes on the GPU.
  *
- * The reader of what libmdct_jpegprog.so (include/mdct_jpegprog.h) writes.  A progressive file codes every component's coefficients in
+ * The reader of what libmdct_jpegprog.so (include/mdct_jpegprog.h) writes (Ah = Al = 0, restart markers in every scan), and of the
+ * files libjpeg's standard scan script gives (Pillow's progressive=True, jpegtran -progressive).  A progressive file codes every component's coefficients in
  * several scans: a DC-first scan (ss = se = 0; one component, or all of them interleaved) and AC-band scans (1 <= ss <= se <= 63, one
  * component each, G.1.1.1.1), whose blocks may end in an end-of-band run (EOBn: this block and run - 1 further ones have no more levels
  * in the band).  A run never crosses a restart interval (G.1.2.2), so every interval is still independent: one workgroup decodes it,
@@ -11,8 +12,19 @@
  * Nothing is allocated or synchronised inside mdct_jpegdec_prog_decode: it may be captured into a hipGraph.  Return codes are those of
  * include/mdct.h; the message of this library's last failure is mdct_jpegdec_prog_last_error().  The library links against
  * libmdct_jpegdec.so and libmdct_hip.so; its launches appear in mdct_kernel_counts().
- * Out of scope, refused and never decoded wrongly: successive approximation (Ah or Al != 0: the caller must not hand such a scan
- * over, the descriptor cannot say it), progressive scans without restart markers, arithmetic coding, 12-bit samples. */
+ *
+ * Successive approximation (G.1.2) codes a coefficient's bits in several scans: a first scan (Ah = 0) gives the levels divided by
+ * 1 << Al, each refinement scan (Ah = Al + 1) one more bit.  Of the five kinds of scan, the two first kinds are decoded as described
+ * above, for any Al.  A DC refinement scan is one raw bit per block: the lanes of the interval's workgroup share its bytes, each
+ * finding its first block by a prefix sum of the data bytes before it.  An AC refinement scan is decoded SEQUENTIALLY inside a restart
+ * interval, by one lane of a one-wave workgroup (the wave loads and stores the blocks): how many bits a symbol consumes depends on
+ * which coefficients of the block earlier scans left non-zero, so the sub-sequence scheme does not apply.  Intervals run in parallel.
+ *
+ * A scan without restart markers is not a kind of its own here: restart_interval == 0 stays refused, and the caller hands such a scan
+ * over as ONE interval (restart_interval = mcus_x * mcus_y, interval_offsets = {0, scan_len} written by the host, no
+ * mdct_jpegdec_index).  That is correct and not fast: one workgroup decodes a whole first or DC refinement scan, one LANE a whole AC
+ * refinement scan (DESIGN.md 4.13 has the measured times).
+ * Out of scope, refused and never decoded wrongly: arithmetic coding, 12-bit samples. */
 #ifndef MDCT_JPEGDEC_PROG_H
 #define MDCT_JPEGDEC_PROG_H
 
@@ -59,6 +71,28 @@ size_t mdct_jpegdec_prog_intervals(const mdct_jpegdec_scan *desc, int ss, int se
  * Other intervals are not touched by it.  The DC predictor wraps as in mdct_jpegdec_decode: the level stored is (int16_t)pred. */
 int mdct_jpegdec_prog_decode(const mdct_jpegdec_scan *desc, int ss, int se, const mdct_jpegdec_tables *tables, const uint8_t *scan,
                              size_t scan_len, const uint64_t *interval_offsets, uint32_t *interval_status, void *stream);
+
+/* The same for a scan with successive approximation (T.81 G.1.2): ah, al as the scan header gives them, 0 <= al <= 13 and ah == 0 (a
+ * first scan) or ah == al + 1 (a refinement scan); anything else is MDCT_INVALID_PARAMETER, refused on the host before any launch, as
+ * is everything mdct_jpegdec_prog_decode refuses.  mdct_jpegdec_prog_decode is the case ah = al = 0 of this function.  One launch.
+ *
+ *   DC first, al > 0       as above; the level stored is (int16_t)(pred << al).
+ *   AC first, al > 0       as above; the level stored is v << al.  Statuses and the zeroing behind a failing block as above.
+ *   DC refinement          one raw bit per block of the interval, in the scan's block order: a set bit ORs 1 << al into position
+ *                          (0, 0).  No table is read: `tables` may be null, and dc_slot is only checked for its range.
+ *   AC refinement          T.81 G.1.2.3, Figure G.7.  A symbol is (run, size) with size 0 or 1, or EOBn.  While `run` positions
+ *                          without history are skipped, every position that is already non-zero consumes one correction bit; a set
+ *                          bit adds +-(1 << al) away from zero where that bit of the coefficient is still clear; a new coefficient
+ *                          is +-(1 << al).  The blocks of an end-of-band run consume the correction bits of their non-zero positions.
+ *                          The component's ac_slot must be present.
+ * interval_status of a refinement interval: as above (exactly the interval's blocks, then 1-bit padding, then RST(k mod 8)); in an AC
+ * refinement a symbol of size > 1 is BAD_CODE, a run (a ZRL's sixteen positions included) that ends past se is COEF_OVERFLOW, an
+ * EOBn that names more blocks than the interval has left is EOBRUN_OVERFLOW.  A refinement interval that fails touches nothing outside
+ * the band and the interval's blocks; the blocks it reached hold unspecified refinements, and NOTHING is set back to zero (that
+ * would destroy what earlier scans decoded): the caller discards the planes. */
+int mdct_jpegdec_prog_decode_approx(const mdct_jpegdec_scan *desc, int ss, int se, int ah, int al,
+                                    const mdct_jpegdec_tables *tables, const uint8_t *scan, size_t scan_len,
+                                    const uint64_t *interval_offsets, uint32_t *interval_status, void *stream);
 
 /* message of this library's last failure */
 const char *mdct_jpegdec_prog_last_error(void);

@@ -1,5 +1,5 @@
 """ctypes binding of libmdct_jpegdec_prog.so -- the C-ABI declared in include/mdct_jpegdec_prog.h (the GPU decoder of a progressive
-file's scans: spectral selection only, with restart markers).
+file's scans: spectral selection and successive approximation).
 
 Its own signature table: a separate library, linked against libmdct_jpegdec.so (whose table handle, scan descriptor and interval index
 it takes) and libmdct_hip.so.  No fallback: if the shared object is missing or fails to load, every entry point raises.
@@ -20,6 +20,8 @@ SIGNATURES = {
     "mdct_jpegdec_prog_intervals": (c_size_t, [ctypes.POINTER(_jpegdec_lib.Scan), c_int, c_int]),
     "mdct_jpegdec_prog_decode": (c_int, [ctypes.POINTER(_jpegdec_lib.Scan), c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p,
                                          c_void_p]),
+    "mdct_jpegdec_prog_decode_approx": (c_int, [ctypes.POINTER(_jpegdec_lib.Scan), c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                                c_void_p, c_void_p, c_void_p]),
     "mdct_jpegdec_prog_last_error": (ctypes.c_char_p, []),
 }
 

@@ -1,5 +1,5 @@
-// jpeg_decode_progressive.hip -- the restart-marked scans of a progressive JPEG with spectral selection only (T.81 Annex G,
-// Ah = Al = 0) -> quantised int16 coefficient planes (include/mdct_jpegdec_prog.h).
+// jpeg_decode_progressive.hip -- the scans of a progressive JPEG (T.81 Annex G: spectral selection and successive approximation), one
+// restart interval per workgroup -> quantised int16 coefficient planes (include/mdct_jpegdec_prog.h).
 //
 // Built into its own library, libmdct_jpegdec_prog.so, linked against libmdct_jpegdec.so (whose table handle, descriptor and interval
 // index it takes) and libmdct_hip.so (whose launch tally counts its launches).
@@ -22,6 +22,17 @@
 // garbage EOBn is simply counted (k_decode's rule: a stopped lane would serialise the interval).
 // There is no zeroing pass: the caller's planes are zero in the band, and only an interval that fails sets the band's positions of the
 // blocks behind the failing one back to zero (the lanes behind the error wrote levels of the re-synchronised decode there).
+//
+// Successive approximation (ProgArgs::ah, al, uniform per launch) adds three scan kinds to the two kernels as runtime branches:
+//   a first scan with al > 0 is the path above, its levels stored shifted left by al;
+//   a DC refinement scan (k_decode_prog_dc, ah > 0) is one raw bit per block and no Huffman code: refine_dc gives every lane the bits
+//   of its own sub-sequence by a workgroup prefix sum of the unstuffed data bytes before it, with no speculation and no settle();
+//   an AC refinement scan (k_decode_prog_ac, ah > 0) is decoded sequentially, one interval per ONE-WAVE workgroup (refine_ac): how
+//   many bits a symbol consumes depends on which coefficients of the block earlier scans left non-zero, so a lane that does not know
+//   its block cannot decode and the sub-sequence scheme does not apply.  The wave loads the block (lane i the band's zig-zag
+//   position i), three ballots hand lane 0 the block's history as 64-bit masks, lane 0 decodes the block's symbols and correction
+//   bits on those masks alone, and the wave applies and stores what changed.
+// A refinement interval that fails is left as it is (zeroing would destroy what earlier scans decoded).
 // Every loop has a bound; no workgroup waits for another.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,6 +53,7 @@ struct ProgArgs
 {
   DecArgs d;
   uint32_t ss, se; // the band, zig-zag
+  uint32_t ah, al; // successive approximation (G.1.2): ah = 0 a first scan, ah = al + 1 a refinement; levels count in units of 1 << al
 };
 
 constexpr uint32_t kMaxCount = 0x7FFFFFFFu; // a lane's block count saturates here (a garbage EOBn adds up to 32767 per symbol)
@@ -143,7 +155,7 @@ __device__ void run(Reader &r, const ProgArgs &a, const DevTables &T, const uint
       if (WRITE)
       {
         pred[comp] += diff;
-        bp[0] = (int16_t)pred[comp];
+        bp[0] = (int16_t)((uint32_t)pred[comp] << a.al);
       }
       ended = 1;
     }
@@ -199,7 +211,7 @@ __device__ void run(Reader &r, const ProgArgs &a, const DevTables &T, const uint
         if (WRITE)
         {
           const uint32_t z = kZigzag[k];
-          bp[(size_t)(z >> 3) * g.pitch[comp] + (z & 7)] = (int16_t)v;
+          bp[(size_t)(z >> 3) * g.pitch[comp] + (z & 7)] = (int16_t)((uint32_t)v << a.al);
         }
         k++;
         ended = k == a.se + 1;
@@ -318,6 +330,317 @@ __device__ __forceinline__ uint32_t first_unit(uint32_t blocks, uint32_t units, 
   return sum < (uint64_t)units + 1 ? (uint32_t)sum : units + 1;
 }
 
+// interval k of the scan: its data [s, e), clamped into the scan whatever the offsets say, its first MCU and its blocks
+struct Interval
+{
+  uint64_t s, e, next;
+  bool last;
+  uint32_t mcu0, units;
+};
+
+__device__ __forceinline__ Interval interval_of(const ProgArgs &a, uint32_t k)
+{
+  Interval iv;
+  const uint64_t len = a.d.scan_len;
+  iv.last = k + 1 == a.d.n_intervals;
+  uint64_t s = a.d.off[k];
+  iv.next = a.d.off[k + 1];
+  uint64_t e = iv.last ? iv.next : (iv.next >= 2 ? iv.next - 2 : 0);
+  s = s < len ? s : len;
+  e = e < len ? e : len;
+  e = e > s ? e : s;
+  // T.81 B.1.1.2: 0xFF bytes directly before the interval's RSTm are fill bytes, not data
+  if (!iv.last && iv.next <= len)
+    for (uint64_t i = 0, n = e - s; i < n && a.d.scan[e - 1] == 0xFF; i++)
+      e--;
+  iv.s = s;
+  iv.e = e;
+  iv.mcu0 = k * a.d.restart;
+  const uint32_t nmcu = (a.d.total_mcus - iv.mcu0) < a.d.restart ? a.d.total_mcus - iv.mcu0 : a.d.restart;
+  iv.units = nmcu * a.d.g.upm;
+  return iv;
+}
+
+// lane 0: the interval's status, once its data is judged: the marker after an interval that is not the last must be RST(k mod 8)
+__device__ __forceinline__ void put_status(const ProgArgs &a, const Interval &iv, uint32_t k, uint32_t st)
+{
+  if (st == MDCT_JPEGDEC_OK && !iv.last)
+  {
+    const uint64_t next = iv.next;
+    const bool ok = next >= 2 && next <= a.d.scan_len && next - 2 >= iv.s && a.d.scan[next - 2] == 0xFF && a.d.scan[next - 1] == 0xD0 + (k & 7);
+    if (!ok)
+      st = MDCT_JPEGDEC_UNEXPECTED_MARKER;
+  }
+  a.d.status[k] = st;
+}
+
+// ------------------------------------------------------------------------------------------------------ DC refinement (G.1.2.1)
+// One raw bit per block in the scan's block order; a set bit ORs 1 << al into position (0, 0).  Every bit is a symbol boundary, so
+// nothing is speculated: lane i counts the unstuffed data bytes of its sub-sequence, a prefix sum gives it the number of its first
+// data byte (bit 8 * that is its first block), and it reads its bytes again and writes.  A 0xFF 0x00 pair may straddle the cut: the
+// 0xFF's lane counts the pair, the next lane skips the zero.  A marker ends the data: the lanes behind its lane write nothing.
+// mark / bad / total: three words of LDS.
+__device__ __forceinline__ void refine_dc(const ProgArgs &a, uint32_t *lcomp, int *wtot, uint32_t *mark, uint32_t *bad, uint32_t *total)
+{
+  const int tid = threadIdx.x;
+  const uint32_t k = blockIdx.x;
+  const BlockPlace &g = a.d.g;
+  if (tid < 16)
+    lcomp[tid] = tid < (int)g.upm ? g.bcomp[tid] : 0;
+  if (tid == 0)
+  {
+    *mark = kNone;
+    *bad = 0;
+    *total = 0;
+  }
+  const Interval iv = interval_of(a, k);
+  const uint64_t s = iv.s, e = iv.e;
+  const uint32_t units = iv.units;
+  const uint32_t need = units / 8 + 1; // data bytes that matter: one more than the blocks' means bits left over
+  uint64_t sb = (e - s + kThreads - 1) / kThreads;
+  sb = sb < 8 ? 8 : sb;
+  uint64_t p0 = s + (uint64_t)tid * sb;
+  p0 = p0 < e ? p0 : e;
+  const uint64_t p1 = e - p0 > sb ? p0 + sb : e;
+  if (tid > 0 && p0 < p1 && a.d.scan[p0] == 0 && a.d.scan[p0 - 1] == 0xFF)
+    p0++; // the stuffed zero of the previous lane's last byte
+  wg_sync();
+
+  // ---- the data bytes of each sub-sequence, up to a marker
+  uint32_t cnt = 0;
+  bool marker = false;
+  for (uint64_t p = p0; p < p1 && cnt <= need; p++)
+  {
+    if (a.d.scan[p] == 0xFF)
+    {
+      if (p + 1 < e && a.d.scan[p + 1] == 0)
+        p++;
+      else
+      {
+        marker = true;
+        break;
+      }
+    }
+    cnt++;
+  }
+  if (marker)
+    atomicMin(mark, (uint32_t)tid);
+  wg_sync();
+  const uint32_t mlane = *mark;
+  const bool dead = (uint32_t)tid > mlane;
+  if (dead)
+    cnt = 0;
+  const uint32_t byte0 = first_unit(cnt, need + 1, wtot); // (clamped to need + 2: beyond that nothing is told apart)
+  if (tid == kThreads - 1)
+    *total = byte0 + cnt < need + 2 ? byte0 + cnt : need + 2;
+
+  // ---- the bits
+  if (!dead)
+  {
+    uint64_t j = byte0; // number of the data byte
+    for (uint64_t p = p0; p < p1 && 8 * j < units; p++, j++)
+    {
+      const uint32_t byte = a.d.scan[p];
+      if (byte == 0xFF)
+      {
+        if (p + 1 < e && a.d.scan[p + 1] == 0)
+          p++;
+        else
+          break;
+      }
+      const uint32_t u0 = (uint32_t)(8 * j), n = units - u0 < 8 ? units - u0 : 8;
+      const uint32_t mcu = iv.mcu0 + u0 / g.upm;
+      uint32_t b = u0 % g.upm, my = mcu / g.mcus_x, mx = mcu - my * g.mcus_x;
+      for (uint32_t t = 0; t < n; t++)
+      {
+        if ((byte >> (7 - t)) & 1)
+        {
+          int16_t *bp = block_at(g, mx, my, b, lcomp[b], 0);
+          bp[0] = (int16_t)(bp[0] | (1 << a.al));
+        }
+        if (++b == g.upm)
+        {
+          b = 0;
+          if (++mx == g.mcus_x)
+          {
+            mx = 0;
+            my++;
+          }
+        }
+      }
+      if (n < 8 && (byte & (0xFFu >> n)) != (0xFFu >> n)) // the padding after the last block's bit: 1-bits
+        *bad = 1;
+    }
+  }
+  wg_sync();
+  if (tid == 0)
+  {
+    const uint64_t bits = 8ull * *total;
+    const uint32_t broken = mlane != kNone ? MDCT_JPEGDEC_UNEXPECTED_MARKER : MDCT_JPEGDEC_OUT_OF_DATA;
+    const uint32_t st = bits < units ? broken : (bits - units >= 8 || *bad) ? MDCT_JPEGDEC_LEFTOVER : mlane != kNone ? broken : MDCT_JPEGDEC_OK;
+    put_status(a, iv, k, st);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------ AC refinement (G.1.2.3)
+// Lane 0: the symbols and correction bits of one block (Figure G.7) on the block's history: bit i of nz says that zig-zag position i
+// is non-zero.  eobrun: blocks of a running end-of-band run, this one included; left: blocks the interval has from this one on.
+// -> add: positions whose correction bit is set; nw / nwneg: positions of new coefficients and which of them are negative.
+// Returns 0 or the MDCT_JPEGDEC_* that stops the interval.  Every trip of every loop moves k on, and k ends at se.
+__device__ __forceinline__ uint32_t refine_block(Reader &r, const DevTables &T, int t, uint32_t ss, uint32_t se, uint64_t nz, uint32_t &eobrun,
+                                                 uint32_t left, uint64_t &add, uint64_t &nw, uint64_t &nwneg)
+{
+  uint32_t k = ss;
+  if (eobrun == 0)
+  {
+    while (k <= se)
+    {
+      refill(r);
+      const int sym = huff(r, T, t);
+      if (sym < 0)
+        return no_code(r);
+      if (overrun(r))
+        return data_error(r);
+      uint32_t run_ = (uint32_t)sym >> 4;
+      const uint32_t sz = (uint32_t)sym & 15;
+      uint32_t negative = 0;
+      if (sz > 1)
+        return MDCT_JPEGDEC_BAD_CODE; // a refinement scan codes one bit of a new coefficient
+      if (sz == 1)
+        negative = get_bits(r, 1) ^ 1u;
+      else if (run_ != 15) // EOBn
+      {
+        const uint32_t n = (1u << run_) + get_bits(r, run_);
+        if (overrun(r))
+          return data_error(r);
+        if (n > left)
+          return MDCT_JPEGDEC_EOBRUN_OVERFLOW;
+        eobrun = n;
+        break;
+      }
+      if (overrun(r))
+        return data_error(r);
+      // over run_ positions without history; every position with history on the way takes a correction bit
+      bool placed = false;
+      for (; k <= se; k++)
+      {
+        if ((nz >> k) & 1)
+        {
+          refill(r);
+          if (get_bits(r, 1))
+            add |= 1ull << k;
+        }
+        else if (run_ == 0)
+        {
+          placed = true;
+          break;
+        }
+        else
+          run_--;
+      }
+      if (overrun(r))
+        return data_error(r);
+      if (!placed)
+        return MDCT_JPEGDEC_COEF_OVERFLOW; // the run (a ZRL's sixteenth position too) ends past se
+      if (sz)
+      {
+        nw |= 1ull << k;
+        nwneg |= (uint64_t)negative << k;
+      }
+      k++;
+    }
+  }
+  if (eobrun > 0)
+  {
+    // the rest of the band: correction bits of the positions with history
+    uint64_t m = k <= se ? nz & ((~0ull >> (63 - se)) & (~0ull << k)) : 0;
+    while (m)
+    {
+      const uint32_t i = (uint32_t)__builtin_ctzll(m);
+      m &= m - 1;
+      refill(r);
+      if (get_bits(r, 1))
+        add |= 1ull << i;
+    }
+    if (overrun(r))
+      return data_error(r);
+    eobrun--;
+  }
+  return 0;
+}
+
+__device__ __forceinline__ uint64_t from_lane0(uint64_t x)
+{
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, 0, 64), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), 0, 64);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// One interval of an AC refinement scan by a workgroup of ONE wave (the launch gives it 64 lanes).  Lane i holds zig-zag position i of
+// the current block; the next block's load is in flight while lane 0 decodes.
+__device__ __forceinline__ void refine_ac(const ProgArgs &a, DevTables &T)
+{
+  const uint32_t tid = threadIdx.x, k = blockIdx.x;
+  const BlockPlace &g = a.d.g;
+  {
+    const uint32_t *src = (const uint32_t *)a.d.tab;
+    uint32_t *dst = (uint32_t *)&T;
+    for (uint32_t i = tid; i < (uint32_t)(sizeof(DevTables) / 4); i += 64)
+      dst[i] = src[i];
+  }
+  const Interval iv = interval_of(a, k);
+  wg_sync();
+  const uint32_t comp = g.bcomp[0], units = iv.units;
+  const int p1 = 1 << a.al;
+  const bool inband = tid >= a.ss && tid <= a.se && tid < 64;
+  const uint32_t z = kZigzag[tid & 63];
+  const size_t zoff = (size_t)(z >> 3) * g.pitch[comp] + (z & 7);
+  Reader r;
+  reader_init(r, a.d, iv.s, iv.e, ~uint64_t(0), true);
+  uint32_t eobrun = 0, st = 0;
+  uint32_t my = iv.mcu0 / g.mcus_x, mx = iv.mcu0 - my * g.mcus_x;
+  int16_t *bp = block_at(g, mx, my, 0, comp, 0);
+  int coef = inband && units ? bp[zoff] : 0;
+  for (uint32_t unit = 0; unit < units; unit++)
+  {
+    int16_t *bq = bp;
+    int coming = 0;
+    if (unit + 1 < units)
+    {
+      if (++mx == g.mcus_x)
+      {
+        mx = 0;
+        my++;
+      }
+      bq = block_at(g, mx, my, 0, comp, 0);
+      coming = inband ? bq[zoff] : 0;
+    }
+    const uint64_t nz = __ballot(coef != 0);
+    uint64_t add = 0, nw = 0, nwneg = 0;
+    if (tid == 0)
+      st = refine_block(r, T, a.d.bac[0], a.ss, a.se, nz, eobrun, units - unit, add, nw, nwneg);
+    add = from_lane0(add);
+    nw = from_lane0(nw);
+    nwneg = from_lane0(nwneg);
+    st = (uint32_t)__shfl((int)st, 0, 64);
+    if (inband)
+    {
+      if (coef != 0)
+      {
+        if (((add >> tid) & 1) && (coef & p1) == 0) // away from zero, where this bit is still clear
+          bp[zoff] = (int16_t)(coef + (coef < 0 ? -p1 : p1));
+      }
+      else if ((nw >> tid) & 1)
+        bp[zoff] = (int16_t)(((nwneg >> tid) & 1) ? -p1 : p1);
+    }
+    if (st)
+      break;
+    bp = bq;
+    coef = coming;
+  }
+  if (tid == 0)
+    put_status(a, iv, k, st ? st : units ? after_last_block(r) : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);
+}
+
 template <bool AC>
 __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T, uint32_t *exit_state, uint32_t *lcomp, int *wtot,
                                                 uint32_t *first_err, uint32_t *fin_word, uint32_t *fail_unit)
@@ -330,24 +653,11 @@ __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T,
     *first_err = kNone;
     *fin_word = kNone;
   }
-  // the interval's data, clamped into the scan whatever the offsets say
-  const uint64_t len = a.d.scan_len;
-  const bool last = k + 1 == a.d.n_intervals;
-  uint64_t s = a.d.off[k];
-  const uint64_t next = a.d.off[k + 1];
-  uint64_t e = last ? next : (next >= 2 ? next - 2 : 0);
-  s = s < len ? s : len;
-  e = e < len ? e : len;
-  e = e > s ? e : s;
-  // T.81 B.1.1.2: 0xFF bytes directly before the interval's RSTm are fill bytes, not data
-  if (!last && next <= len)
-    for (uint64_t i = 0, n = e - s; i < n && a.d.scan[e - 1] == 0xFF; i++)
-      e--;
+  const Interval iv = interval_of(a, k);
+  const uint64_t s = iv.s, e = iv.e;
   const uint64_t sb = (e - s + kThreads - 1) / kThreads;
   const SubLane q = sub_lane(s, e, sb < 8 ? 8 : sb, tid, true);
-  const uint32_t mcu0 = k * a.d.restart;
-  const uint32_t nmcu = (a.d.total_mcus - mcu0) < a.d.restart ? a.d.total_mcus - mcu0 : a.d.restart;
-  const uint32_t units = nmcu * a.d.g.upm;
+  const uint32_t mcu0 = iv.mcu0, units = iv.units;
   wg_sync();
 
   // ---- synchronisation: lane 0 starts exact (the band's first position of an MCU's first block), the others from the same guess
@@ -389,15 +699,8 @@ __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T,
   }
   if (tid == 0)
   {
-    uint32_t st = *first_err != kNone ? (*first_err & 0xFF) : (*fin_word != kNone ? *fin_word : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);
-    if (st == MDCT_JPEGDEC_OK && !last)
-    {
-      // the marker after the interval must be RST(k mod 8)
-      const bool ok = next >= 2 && next <= len && next - 2 >= s && a.d.scan[next - 2] == 0xFF && a.d.scan[next - 1] == 0xD0 + (k & 7);
-      if (!ok)
-        st = MDCT_JPEGDEC_UNEXPECTED_MARKER;
-    }
-    a.d.status[k] = st;
+    const uint32_t st = *first_err != kNone ? (*first_err & 0xFF) : (*fin_word != kNone ? *fin_word : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);
+    put_status(a, iv, k, st);
   }
 }
 
@@ -409,6 +712,14 @@ __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T,
     __shared__ uint32_t lcomp[16];                                                                                                        \
     __shared__ int wtot[kThreads / 64];                                                                                                   \
     __shared__ uint32_t first_err, fin_word, fail_unit;                                                                                   \
+    if (a.ah) /* a refinement scan (uniform) */                                                                                           \
+    {                                                                                                                                     \
+      if (AC)                                                                                                                             \
+        refine_ac(a, T);                                                                                                                  \
+      else                                                                                                                                \
+        refine_dc(a, lcomp, wtot, &first_err, &fin_word, &fail_unit);                                                                     \
+      return;                                                                                                                             \
+    }                                                                                                                                     \
     decode_interval<AC>(a, T, exit_state, lcomp, wtot, &first_err, &fin_word, &fail_unit);                                                \
   }
 
@@ -453,21 +764,28 @@ size_t mdct_jpegdec_prog_intervals(const mdct_jpegdec_scan *desc, int ss, int se
   return check_prog(desc, ss, se, d, &n) ? 0 : n;
 }
 
-int mdct_jpegdec_prog_decode(const mdct_jpegdec_scan *desc, int ss, int se, const mdct_jpegdec_tables *tables, const uint8_t *scan,
-                             size_t scan_len, const uint64_t *interval_offsets, uint32_t *interval_status, void *stream)
+int mdct_jpegdec_prog_decode_approx(const mdct_jpegdec_scan *desc, int ss, int se, int ah, int al, const mdct_jpegdec_tables *tables,
+                                    const uint8_t *scan, size_t scan_len, const uint64_t *interval_offsets, uint32_t *interval_status, void *stream)
 {
   mdct_jpegdec_scan d;
   size_t n = 0;
   int rc = check_prog(desc, ss, se, d, &n);
   if (rc)
     return rc;
-  if (!tables || !interval_offsets || !interval_status || (!scan && scan_len))
+  if (al < 0 || al > 13)
+    return fail(MDCT_INVALID_PARAMETER, "successive approximation: Al %d (0..13)", al);
+  if (ah != 0 && ah != al + 1)
+    return fail(MDCT_INVALID_PARAMETER, "successive approximation: Ah %d with Al %d (0: a first scan; Al + 1: a refinement scan)", ah, al);
+  const bool ac = ss > 0, no_table = !ac && ah != 0; // a DC refinement scan is raw bits
+  if ((!tables && !no_table) || !interval_offsets || !interval_status || (!scan && scan_len))
     return fail(MDCT_INVALID_PARAMETER, "null tables / scan / offsets / status");
-  const bool ac = ss > 0;
   // only the slots of the band's class must be present: the other class counts as present for fill_geometry and is never read
-  mdct_jpegdec_tables used = *tables;
+  mdct_jpegdec_tables used;
+  memset(&used, 0, sizeof(used));
+  if (tables)
+    used = *tables;
   for (int t = 0; t < 4; t++)
-    if ((t >= 2) != ac)
+    if ((t >= 2) != ac || no_table)
       used.present[t] = true;
   prog::ProgArgs a;
   memset(&a, 0, sizeof(a));
@@ -481,12 +799,20 @@ int mdct_jpegdec_prog_decode(const mdct_jpegdec_scan *desc, int ss, int se, cons
   a.d.n_intervals = (uint32_t)n;
   a.ss = (uint32_t)ss;
   a.se = (uint32_t)se;
-  if (ac)
-    MDCT_LAUNCH(prog::k_decode_prog_ac, dim3((uint32_t)n), dim3(kThreads), 0, (hipStream_t)stream, a);
+  a.ah = (uint32_t)ah;
+  a.al = (uint32_t)al;
+  if (ac) // a refinement scan: one wave per interval, whose lane 0 decodes (refine_ac)
+    MDCT_LAUNCH(prog::k_decode_prog_ac, dim3((uint32_t)n), dim3(ah ? 64 : kThreads), 0, (hipStream_t)stream, a);
   else
     MDCT_LAUNCH(prog::k_decode_prog_dc, dim3((uint32_t)n), dim3(kThreads), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MDCT_SUCCESS : hip_fail(e, "progressive decode launch");
+}
+
+int mdct_jpegdec_prog_decode(const mdct_jpegdec_scan *desc, int ss, int se, const mdct_jpegdec_tables *tables, const uint8_t *scan,
+                             size_t scan_len, const uint64_t *interval_offsets, uint32_t *interval_status, void *stream)
+{
+  return mdct_jpegdec_prog_decode_approx(desc, ss, se, 0, 0, tables, scan, scan_len, interval_offsets, interval_status, stream);
 }
 
 } // extern "C"

@@ -1,10 +1,12 @@
-"""Baseline and progressive (spectral selection) JPEG -> 8-bit planes on the GPU (libmdct_jpegdec.so, include/mdct_jpegdec.h;
-libmdct_jpegdec_unmarked.so, include/mdct_jpegdec_unmarked.h; libmdct_jpegdec_prog.so, include/mdct_jpegdec_prog.h).
+"""Baseline and progressive (spectral selection, successive approximation) JPEG -> 8-bit planes on the GPU (libmdct_jpegdec.so,
+include/mdct_jpegdec.h; libmdct_jpegdec_unmarked.so, include/mdct_jpegdec_unmarked.h; libmdct_jpegdec_prog.so,
+include/mdct_jpegdec_prog.h).
 
-decode_jpeg parses the file on the host (read_file: jfif.read_jpeg, or jfif.read_progressive_jpeg for a SOF2 file), uploads each scan
+decode_jpeg parses the file on the host (read_file: jfif.read_jpeg, or jfif_sof2.read_sof2_jpeg for a SOF2 file), uploads each scan
 and decodes it into quantised int16 coefficient planes: a baseline scan with restart markers by finding its restart intervals
 (mdct_jpegdec_index) and decoding them (mdct_jpegdec_decode), one without by mdct_jpegdec_decode_unmarked, a scan of a progressive
-file by mdct_jpegdec_index and mdct_jpegdec_prog_decode into its band of the planes.  It checks every scan's status, and runs
+file by mdct_jpegdec_index (unless it has no restart markers: then it is one interval) and mdct_jpegdec_prog_decode_approx into its
+band, and its bit, of the planes.  It checks every scan's status, and runs
 mdct_inv_i16_u8_batch over the planes with each component's DQT as the table.  One uint8 plane per component, cropped to the
 component's size (T.81 A.1.1).  With mode="RGB" the planes go through one more launch, mdct_jpegcolor_to_rgb
 (libmdct_jpegcolor.so, include/mdct_jpegcolor.h): chroma upsampling and YCbCr -> RGB as libjpeg-turbo's default decode gives them.
@@ -19,7 +21,7 @@ import ctypes
 
 import numpy as np
 
-from . import _jpegcolor_lib, _jpegdec_batch_lib, _jpegdec_lib, _jpegdec_prog_lib, _jpegdec_unmarked_lib, api, jfif
+from . import _jpegcolor_lib, _jpegdec_batch_lib, _jpegdec_lib, _jpegdec_prog_lib, _jpegdec_unmarked_lib, api, jfif, jfif_sof2
 from .api import _ptr, _stream
 
 
@@ -142,18 +144,21 @@ def prog_intervals(desc, ss, se):
     return n
 
 
-def decode_prog(desc, ss, se, tables, scan, offsets, status, scan_len=None, stream=None):
-    """mdct_jpegdec_prog_decode: one scan of a progressive file, band ss..se; offsets as index() leaves them"""
+def decode_prog(desc, ss, se, tables, scan, offsets, status, scan_len=None, stream=None, *, ah=0, al=0):
+    """mdct_jpegdec_prog_decode_approx: one scan of a progressive file, band ss..se, successive approximation ah / al; offsets as
+    index() leaves them, or [0, scan_len] for a scan without restart markers handed over as one interval (markerless_desc).
+    tables: None for a DC refinement scan, which reads no table"""
     L = scan.numel() if scan_len is None else scan_len
-    _jpegdec_prog_lib.LIB.check(_jpegdec_prog_lib.load().mdct_jpegdec_prog_decode(ctypes.byref(desc), ss, se, tables.handle, _ptr(scan), L, _ptr(offsets),
-                                                                                  _ptr(status), _stream(stream)))
+    lib = _jpegdec_prog_lib.load()
+    _jpegdec_prog_lib.LIB.check(lib.mdct_jpegdec_prog_decode_approx(ctypes.byref(desc), ss, se, ah, al, None if tables is None else tables.handle,
+                                                                    _ptr(scan), L, _ptr(offsets), _ptr(status), _stream(stream)))
 
 
 def read_file(data):
-    """the parser the file's frame header asks for: jfif.read_progressive_jpeg for SOF2, jfif.read_jpeg(require_restart=False) for
+    """the parser the file's frame header asks for: jfif_sof2.read_sof2_jpeg for SOF2, jfif.read_jpeg(require_restart=False) for
     everything else (which refuses what it always refused)"""
     if jfif.sof_marker(data) == 0xC2:
-        return jfif.read_progressive_jpeg(data)
+        return jfif_sof2.read_sof2_jpeg(data)
     return jfif.read_jpeg(data, require_restart=False)
 
 
@@ -183,7 +188,9 @@ def scan_plan(info, si, sc, geo, grid, coefs):
     """Everything decode_jpeg settles about scan si on the host before its first launch: the Huffman specifications the scan names
     (JpegFormatError for one that is not defined), their validation (tables_check) and the descriptor over the coefficient planes,
     which the library it goes to must accept (MdctError).  coefs: one int16 tensor per component, [rows, blocks_x * 8].
-    A scan of a progressive file (one with 'ss' / 'se') names only the tables of its band's class: DC for 0..0, AC for an AC band.
+    A scan of a progressive file (one with 'ss' / 'se') names only the tables of its band's class: DC for 0..0, AC for an AC band,
+    none for a DC refinement scan (Ah > 0), which is raw bits.  One without restart markers is described as ONE restart interval
+    (restart_interval = mcus_x * mcus_y: the library has no other way to take it, and decode_scan writes its two offsets itself).
     -> (specs, desc)"""
     mcus_x, mcus_y, members = scan_geometry(info, sc, geo, grid)
     specs = [None] * 4
@@ -191,15 +198,18 @@ def scan_plan(info, si, sc, geo, grid, coefs):
     band = (sc["ss"], sc["se"]) if "ss" in sc else None
     for c, (ci, h, v) in zip(sc["components"], members):
         dc, ac = (c["td"], (0, c["td"])), (2 + c["ta"], (1, c["ta"]))
-        for slot, key in (dc, ac) if band is None else (dc,) if band == (0, 0) else (ac,):
+        for slot, key in (dc, ac) if band is None else (ac,) if band != (0, 0) else (dc,) if sc.get("ah", 0) == 0 else ():
             if key not in sc["huffman"]:
                 raise jfif.JpegFormatError(f"scan {si} uses Huffman table {key} that is not defined")
             specs[slot] = sc["huffman"][key]
         planes.append((coefs[ci], geo[ci][2], geo[ci][3], h, v, c["td"], 2 + c["ta"]))
     if tables_check(specs) != 0:
         raise api.MdctError(f"scan {si}: {last_error()}")
-    desc = scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"])
+    desc = scan_desc(planes, mcus_x, mcus_y, sc["restart_interval"] or mcus_x * mcus_y if band is not None else sc["restart_interval"])
     if band is not None:
+        if band == (0, 0) and sc.get("ah", 0):  # the slot no table stands behind is still checked for its range
+            for c in range(desc.n_components):
+                desc.comp[c].dc_slot = 0
         prog_intervals(desc, *band)
     elif sc["restart_interval"]:
         n_intervals(desc)
@@ -330,19 +340,21 @@ def decode_coefficients(data, device=None, stream=None, *, info=None):
         coefs = [torch.zeros((by * 8, bx * 8), dtype=torch.int16, device=dev) for _, _, bx, by in geo]
         for si, sc in enumerate(info["scans"]):
             specs, desc = scan_plan(info, si, sc, geo, grid, coefs)
-            tables = Tables(specs)
+            tables = Tables(specs) if any(sp is not None for sp in specs) else None  # (a DC refinement scan reads no table)
             seg = torch.frombuffer(bytearray(raw[sc["start"]:sc["end"]]) or bytearray(1), dtype=torch.uint8).to(dev, non_blocking=False)
             try:
                 decode_scan(torch, si, sc, desc, tables, seg, dev, stream)
             finally:
-                tables.close()
+                if tables is not None:
+                    tables.close()
     return info, coefs
 
 
 def decode_jpeg(data, device=None, coefficients=False, stream=None, *, mode=None, layout="HWC", scale_denom=1):
-    """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file), or a progressive one
-    that uses spectral selection only and carries restart markers (jfif.read_progressive_jpeg: what encode_jpeg(progressive=True)
-    writes; successive approximation is refused).  Returns one uint8
+    """Decode a baseline JPEG on the GPU, with or without restart markers (scans of both kinds may share a file), or a progressive
+    Huffman one (jfif_sof2.read_sof2_jpeg: spectral selection and successive approximation, with or without restart markers -- what
+    encode_jpeg(progressive=True) writes and what libjpeg's standard scan script, Pillow's progressive=True, writes; AC refinement scans
+    are decoded sequentially inside a restart interval and a scan without markers is one interval: correct, not fast).  Returns one uint8
     tensor [height, width] per component (cropped to its true size); with coefficients=True also the quantised int16 coefficient planes
     ([blocks_y * 8, blocks_x * 8], padded to the MCU grid): (planes, coefficient planes).
     mode="RGB" returns one uint8 image instead of the planes, [height, width, 3] (layout="HWC") or [3, height, width] (layout="CHW"),
@@ -674,6 +686,9 @@ def decode_scan(torch, si, sc, desc, tables, seg, dev, stream=None):
     which always converges).  Returns the status; JpegDecodeError for a scan that did not decode cleanly."""
     with api._on_stream(stream, dev):
         L = sc["end"] - sc["start"]
+        band = (sc["ss"], sc["se"]) if "ss" in sc else None
+        if band is not None:
+            return _decode_prog_scan(torch, si, sc, band, desc, tables, seg, L, dev, stream)
         if sc["restart_interval"] == 0:
             nbytes = unmarked_workspace(desc, L)
             if nbytes == 0:
@@ -690,19 +705,38 @@ def decode_scan(torch, si, sc, desc, tables, seg, dev, stream=None):
                 raise JpegDecodeError(f"scan {si} (no restart markers): {_jpegdec_unmarked_lib.STATUS_NAMES.get(int(st[0]), int(st[0]))} "
                                       f"after {int(st[1])} blocks", scan=si, status=st)
             return st
-        band = (sc["ss"], sc["se"]) if "ss" in sc else None
-        n = n_intervals(desc) if band is None else prog_intervals(desc, *band)
+        n = n_intervals(desc)
         off = torch.empty(n + 1, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
         index(seg, n, off, status, scan_len=L, stream=stream)
-        if band is None:
-            decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
-        else:
-            decode_prog(desc, band[0], band[1], tables, seg, off, status, scan_len=L, stream=stream)
+        decode(desc, tables, seg, off, status, scan_len=L, stream=stream)
         st = status.cpu().numpy()
         bad = np.flatnonzero(st)
         if bad.size:
             k = int(bad[0])
-            raise JpegDecodeError(f"scan {si}{'' if band is None else f' (band {band[0]}..{band[1]})'}: {bad.size} of {n} restart intervals failed; "
+            raise JpegDecodeError(f"scan {si}: {bad.size} of {n} restart intervals failed; "
                                   f"interval {k}: {STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
         return st
+
+
+def _decode_prog_scan(torch, si, sc, band, desc, tables, seg, L, dev, stream):
+    """decode_scan for a scan of a progressive file: the interval index, unless the scan has no restart markers -- then it is one
+    interval, whose two offsets the host writes -- and one decode launch"""
+    ah, al = sc.get("ah", 0), sc.get("al", 0)
+    n = prog_intervals(desc, *band)
+    with api._on_stream(stream, dev):
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        if sc["restart_interval"] == 0:
+            off = torch.tensor([0, L], dtype=torch.int64).to(dev, non_blocking=False)
+        else:
+            off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            index(seg, n, off, status, scan_len=L, stream=stream)
+        decode_prog(desc, band[0], band[1], tables, seg, off, status, scan_len=L, stream=stream, ah=ah, al=al)
+        st = status.cpu().numpy()
+    bad = np.flatnonzero(st)
+    if bad.size:
+        k = int(bad[0])
+        approx = f", Ah {ah} Al {al}" if ah or al else ""
+        raise JpegDecodeError(f"scan {si} (band {band[0]}..{band[1]}{approx}): {bad.size} of {n} restart intervals failed; "
+                              f"interval {k}: {STATUS_NAMES.get(int(st[k]), int(st[k]))}", scan=si, status=st)
+    return st
