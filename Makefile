@@ -36,7 +36,7 @@ tools/mdct_jpeg: tools/mdct_jpeg.c include/mdct.h
 # (simd_dct_amd/_<library without mdct_>_lib.py binds it and names the same libraries in `after`; tests/test_bindings.py compares)
 JPEG_ROWS += mdct_jpegdec:jpeg_decode.hip:  # the decoder of restart-marked scans (include/mdct_jpegdec.h)
 JPEG_ROWS += mdct_jpegdec_unmarked:jpeg_decode_unmarked.hip:mdct_jpegdec  # ... of scans without markers
-JPEG_ROWS += mdct_jpegdec_prog:jpeg_decode_progressive.hip:mdct_jpegdec  # ... of a progressive file's scans (spectral selection)
+JPEG_ROWS += mdct_jpegdec_prog:jpeg_decode_progressive.hip:mdct_jpegdec  # ... of a progressive file's scans (spectral selection, successive approximation)
 JPEG_ROWS += mdct_jpegdec_batch:jpeg_decode_batch.hip:  # ... of the restart-marked scans of many files, four launches in all
 JPEG_ROWS += mdct_jpegcolor:jpeg_color.hip:  # chroma upsampling, YCbCr -> RGB
 JPEG_ROWS += mdct_jpegscale:jpeg_idct_scaled.hip:  # the inverse at 1/2, 1/4, 1/8 size

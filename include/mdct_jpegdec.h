@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-/* interval_status values written by mdct_jpegdec_decode */
+/* interval_status values written by mdct_jpegdec_decode (6 is MDCT_JPEGDEC_NOT_SYNCHRONISED of mdct_jpegdec_unmarked.h) */
 enum
 {
   MDCT_JPEGDEC_OK = 0,                /* exactly the interval's MCUs, then its own 1-bit padding up to the interval's end */
@@ -36,7 +36,8 @@ enum
   MDCT_JPEGDEC_BAD_CODE = 2,          /* a bit pattern that is no code of the Huffman table in use */
   MDCT_JPEGDEC_COEF_OVERFLOW = 3,     /* a run / ZRL that moves the coefficient index beyond 63 */
   MDCT_JPEGDEC_UNEXPECTED_MARKER = 4, /* a marker inside the interval's data, or the marker after it is not RST(k mod 8) */
-  MDCT_JPEGDEC_LEFTOVER = 5           /* data after the last MCU that is more than the interval's padding */
+  MDCT_JPEGDEC_LEFTOVER = 5,          /* data after the last MCU that is more than the interval's padding */
+  MDCT_JPEGDEC_EOBRUN_OVERFLOW = 7    /* progressive scans (mdct_jpegdec_prog.h): an end-of-band run that reaches past the interval's last block */
 };
 
 #define MDCT_JPEGDEC_MAX_COMPONENTS 3

@@ -34,9 +34,6 @@
 extern "C" {
 #endif
 
-/* one more interval status beside MDCT_JPEGDEC_* (6 is MDCT_JPEGDEC_NOT_SYNCHRONISED of mdct_jpegdec_unmarked.h) */
-#define MDCT_JPEGDEC_EOBRUN_OVERFLOW 7 /* an end-of-band run that reaches past the interval's last block */
-
 /* What the band (ss, se) asks of the descriptor:
  *   ss == se == 0          a DC-first scan: 1..3 components, interleaved with the descriptor's sampling factors (at most 10 blocks per
  *                          MCU) or one component with h = v = 1 over its own block grid.  Only dc_slot is used (0..1, present in the

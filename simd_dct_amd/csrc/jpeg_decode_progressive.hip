@@ -7,19 +7,13 @@
 //   k_decode_prog_dc   a DC-first scan (ss = se = 0), one workgroup per restart interval
 //   k_decode_prog_ac   an AC-band scan (1 <= ss <= se <= 63, one component), one workgroup per restart interval
 //
-// Both are k_decode's model (jpeg_decode.hip) over another symbol grammar: the interval's stuffed bytes are cut into kThreads
-// sub-sequences, lane i decodes its own from a guessed state and on to the first symbol boundary past its end, lane i + 1 decodes again
-// while the state it started from differs from that exit, prefix sums over the lanes give every lane its first block (and the DC
-// predictors there), and a last pass decodes exactly and writes.  From jpegdec_common.h come the bit reader, the Huffman lookup, the
-// sub-sequence cut, the table load and the prefix sum; run, speculate, settle and write_pass are this file's own, because the common
-// ones are written around the baseline grammar (DC, then AC to 63, per block) and are not to change under k_decode and k_um_*.
+// Both are k_decode's model (jpeg_decode.hip) over another symbol grammar, Band<AC>, and made of jpegdec_common.h's pieces: the bit
+// reader, the Huffman lookup, run, speculate, settle and write_pass, the interval's bookkeeping (interval_of, put_status,
+// after_last_block), the table load and the prefix sum.  This file's own are the clamped prefix of the block counts (first_unit),
+// decode_interval<AC> and the refinement scans.
 //
-// The state between two symbols is (bits past the next sub-sequence's first data byte, k, block in MCU) as in k_decode: k is 0 in a DC
-// scan and ss..se in an AC band, the block in MCU is 0 in an AC band.  An end-of-band run is accounted whole where its EOBn token is
-// decoded: the lane's block count grows by the run and k returns to ss, so no pending run lives across a symbol boundary, the state
-// stays one 32-bit word, and the prefix sum of the block counts is exact.  The write pass jumps over the run's blocks.
-// While speculating, an invalid code (skip one bit), a level run or a ZRL past se ends the block instead of stopping the lane, and a
-// garbage EOBn is simply counted (k_decode's rule: a stopped lane would serialise the interval).
+// The state between two symbols is k_decode's: k is 0 in a DC scan and ss..se in an AC band, whose block in MCU is 0.  An end-of-band
+// run is accounted whole where its EOBn is decoded, so the prefix sum of the block counts is exact (a garbage EOBn is simply counted).
 // There is no zeroing pass: the caller's planes are zero in the band, and only an interval that fails sets the band's positions of the
 // blocks behind the failing one back to zero (the lanes behind the error wrote levels of the re-synchronised decode there).
 //
@@ -56,269 +50,6 @@ struct ProgArgs
   uint32_t ah, al; // successive approximation (G.1.2): ah = 0 a first scan, ah = al + 1 a refinement; levels count in units of 1 << al
 };
 
-constexpr uint32_t kMaxCount = 0x7FFFFFFFu; // a lane's block count saturates here (a garbage EOBn adds up to 32767 per symbol)
-
-struct PLane
-{
-  uint32_t state;  // packed start / exit state: kErr | d << 12 | k << 4 | b
-  uint32_t blocks; // blocks completed, end-of-band runs included (saturating)
-  int dc[3];       // sum of the DC differences per component
-  uint32_t err;    // MDCT_JPEGDEC_* of a decode error (final pass)
-  bool finished;   // completed the interval's last block (final pass)
-  uint32_t fin;    // status after the last block: OK / LEFTOVER / UNEXPECTED_MARKER
-};
-
-// the interval's last block is complete: what follows must be its padding (1-bits to the byte boundary) and nothing else
-__device__ __forceinline__ uint32_t after_last_block(Reader &r)
-{
-  refill(r);
-  if (r.dry)
-  {
-    const uint32_t rem = r.uend - r.u;
-    if (rem < 8 && (rem == 0 || (uint32_t)(r.buf >> (64 - rem)) == (1u << rem) - 1u))
-      return r.marker ? MDCT_JPEGDEC_UNEXPECTED_MARKER : MDCT_JPEGDEC_OK;
-  }
-  return MDCT_JPEGDEC_LEFTOVER;
-}
-
-// Decode from state `start` until the first symbol boundary at or after the next sub-sequence's start (a lane with a successor), the
-// interval's last block (WRITE with a unit budget), or an error.  WRITE: unit0 blocks precede the start; pred = DC predictors there.
-template <bool AC, bool WRITE>
-__device__ void run(Reader &r, const ProgArgs &a, const DevTables &T, const uint32_t *lcomp, uint32_t start, PLane &out, uint32_t unit0,
-                    uint32_t units, uint32_t mcu0, int pred[3], uint64_t cap)
-{
-  const BlockPlace &g = a.d.g;
-  out.blocks = 0;
-  out.dc[0] = out.dc[1] = out.dc[2] = 0;
-  out.err = 0;
-  out.finished = false;
-  out.fin = 0;
-  out.state = kErr;
-  if (start & kErr)
-    return;
-  uint32_t k = (start >> 4) & 0x7F, b = start & 0xF;
-  uint32_t d = start >> 12;
-  for (uint32_t i = 0; i < 64 && d > 0; i++) // skip the bits the previous lane consumed past this sub-sequence's start
-  {
-    refill(r);
-    const uint32_t n = d < 32 ? d : 32;
-    consume(r, n);
-    d -= n;
-  }
-  if (overrun(r))
-  {
-    out.err = data_error(r);
-    return;
-  }
-  uint32_t unit = unit0;
-  if (WRITE && unit >= units)
-    return;
-  uint32_t mx = 0, my = 0;
-  int16_t *bp = nullptr;
-  uint32_t comp = lcomp[b];
-  if (WRITE)
-  {
-    const uint32_t mcu = mcu0 + unit / g.upm;
-    my = mcu / g.mcus_x;
-    mx = mcu - my * g.mcus_x;
-    bp = block_at(g, mx, my, b, comp, 0);
-  }
-  for (uint64_t it = 0; it < cap; it++)
-  {
-    refill(r);
-    if (r.uE != kNone && r.u >= r.uE)
-    {
-      out.state = ((r.u - r.uE) << 12) | (k << 4) | b;
-      return;
-    }
-    uint32_t ended = 0; // blocks this symbol completes
-    const int sym = huff(r, T, AC ? a.d.bac[0] : a.d.bdc[b]);
-    if (sym < 0)
-    {
-      out.err = no_code(r);
-      if (WRITE || out.err != MDCT_JPEGDEC_BAD_CODE)
-        return;
-      consume(r, 1); // speculating: resynchronise instead of stopping
-      out.err = 0;
-      ended = 1;
-    }
-    else if (!AC)
-    {
-      const uint32_t s = (uint32_t)sym & 15;
-      const int diff = extend(get_bits(r, s), s);
-      if (overrun(r))
-      {
-        out.err = data_error(r);
-        return;
-      }
-      out.dc[comp] += diff;
-      if (WRITE)
-      {
-        pred[comp] += diff;
-        bp[0] = (int16_t)((uint32_t)pred[comp] << a.al);
-      }
-      ended = 1;
-    }
-    else
-    {
-      if (overrun(r))
-      {
-        out.err = data_error(r);
-        return;
-      }
-      const uint32_t run_ = (uint32_t)sym >> 4, s = (uint32_t)sym & 15;
-      if (s == 0 && run_ == 15) // ZRL
-      {
-        k += 16;
-        if (k > a.se + 1)
-        {
-          if (WRITE)
-          {
-            out.err = MDCT_JPEGDEC_COEF_OVERFLOW;
-            return;
-          }
-          k = a.se + 1; // speculating: end the block
-        }
-        ended = k == a.se + 1;
-      }
-      else if (s == 0) // EOBn: this block and (1 << n) + extra - 1 further ones
-      {
-        ended = (1u << run_) + get_bits(r, run_);
-        if (overrun(r))
-        {
-          out.err = data_error(r);
-          return;
-        }
-      }
-      else
-      {
-        k += run_;
-        if (k > a.se)
-        {
-          if (WRITE)
-          {
-            out.err = MDCT_JPEGDEC_COEF_OVERFLOW;
-            return;
-          }
-          k = a.se; // speculating: keep the bit position, end the block after this level
-        }
-        const int v = extend(get_bits(r, s), s);
-        if (overrun(r))
-        {
-          out.err = data_error(r);
-          return;
-        }
-        if (WRITE)
-        {
-          const uint32_t z = kZigzag[k];
-          bp[(size_t)(z >> 3) * g.pitch[comp] + (z & 7)] = (int16_t)((uint32_t)v << a.al);
-        }
-        k++;
-        ended = k == a.se + 1;
-      }
-    }
-    if (ended)
-    {
-      k = a.ss;
-      if (WRITE && ended > units - unit) // unit < units here; the block of the EOBn is the failing one
-      {
-        out.err = MDCT_JPEGDEC_EOBRUN_OVERFLOW;
-        return;
-      }
-      out.blocks = out.blocks + ended < kMaxCount ? out.blocks + ended : kMaxCount;
-      if (!AC)
-      {
-        if (++b == g.upm)
-          b = 0;
-        comp = lcomp[b];
-      }
-      if (WRITE)
-      {
-        unit += ended;
-        if (unit == units)
-        {
-          out.finished = true;
-          out.fin = after_last_block(r);
-          return;
-        }
-        if (ended == 1)
-        {
-          if (b == 0 && ++mx == g.mcus_x)
-          {
-            mx = 0;
-            my++;
-          }
-        }
-        else // AC only (one block per MCU): over the run's blocks
-        {
-          const uint32_t mcu = mcu0 + unit;
-          my = mcu / g.mcus_x;
-          mx = mcu - my * g.mcus_x;
-        }
-        bp = block_at(g, mx, my, b, comp, 0);
-      }
-    }
-  }
-  out.err = MDCT_JPEGDEC_OUT_OF_DATA; // not reached: every symbol consumes a bit and the data ends
-}
-
-// one speculating decode of the lane's sub-sequence from state `start`; a lane without data publishes no usable exit and counts nothing
-template <bool AC>
-__device__ __forceinline__ void speculate(const ProgArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t start, PLane &L)
-{
-  Reader r;
-  int dummy[3] = {0, 0, 0};
-  L.state = kErr;
-  L.blocks = 0;
-  L.dc[0] = L.dc[1] = L.dc[2] = 0;
-  if (!q.active)
-    return;
-  reader_init(r, a.d, q.s0, q.end, q.E, q.first);
-  run<AC, false>(r, a, T, lcomp, start, L, 0, 0, 0, dummy, q.cap);
-}
-
-// lane 0 wants want0, lane i the exit of lane i - 1; a lane whose start differs decodes again, until no start changes (at most nact + 1
-// trips: each trip makes one more lane exact).  exit_state: kThreads words of LDS.
-template <bool AC>
-__device__ __forceinline__ void settle(const ProgArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t want0,
-                                       uint32_t &my_start, PLane &L, uint32_t *exit_state)
-{
-  exit_state[threadIdx.x] = L.state;
-  for (uint32_t round = 0; round <= q.nact; round++)
-  {
-    wg_sync();
-    const uint32_t want = threadIdx.x == 0 ? want0 : exit_state[threadIdx.x - 1];
-    const bool changed = q.active && want != my_start;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!__syncthreads_or(changed))
-      break;
-    if (changed)
-    {
-      my_start = want;
-      speculate<AC>(a, T, lcomp, q, my_start, L);
-      exit_state[threadIdx.x] = L.state;
-    }
-  }
-  wg_sync();
-}
-
-// The write pass of a lane with data: the exact decode from `start`.  A decode error goes to *first_err (LDS, kNone before) as
-// lane << 8 | code, the smallest winning; the status after the interval's last block to *fin.  Returns the unit the lane stopped in.
-template <bool AC>
-__device__ __forceinline__ uint32_t write_pass(const ProgArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t start,
-                                               uint32_t unit0, uint32_t units, uint32_t mcu0, int pred[3], uint32_t *first_err, uint32_t *fin)
-{
-  Reader r;
-  PLane F;
-  reader_init(r, a.d, q.s0, q.end, q.E, q.first);
-  run<AC, true>(r, a, T, lcomp, start, F, unit0, units, mcu0, pred, q.cap);
-  if (F.err && unit0 < units)
-    atomicMin(first_err, ((uint32_t)threadIdx.x << 8) | F.err);
-  if (F.finished)
-    *fin = F.fin;
-  return unit0 + F.blocks;
-}
-
 // blocks before each lane's start.  A lane's count is clamped to units + 1 and the sum too, so that counts of garbage (lanes behind an
 // error, whose end-of-band runs mean nothing) can neither wrap nor bring a later lane back inside the interval; the counts are summed
 // in two 16-bit halves, each of which stays far inside wg_excl_scan's int.
@@ -328,50 +59,6 @@ __device__ __forceinline__ uint32_t first_unit(uint32_t blocks, uint32_t units, 
   const uint64_t lo = (uint32_t)wg_excl_scan((int)(c & 0xFFFFu), wtot), hi = (uint32_t)wg_excl_scan((int)(c >> 16), wtot);
   const uint64_t sum = (hi << 16) + lo;
   return sum < (uint64_t)units + 1 ? (uint32_t)sum : units + 1;
-}
-
-// interval k of the scan: its data [s, e), clamped into the scan whatever the offsets say, its first MCU and its blocks
-struct Interval
-{
-  uint64_t s, e, next;
-  bool last;
-  uint32_t mcu0, units;
-};
-
-__device__ __forceinline__ Interval interval_of(const ProgArgs &a, uint32_t k)
-{
-  Interval iv;
-  const uint64_t len = a.d.scan_len;
-  iv.last = k + 1 == a.d.n_intervals;
-  uint64_t s = a.d.off[k];
-  iv.next = a.d.off[k + 1];
-  uint64_t e = iv.last ? iv.next : (iv.next >= 2 ? iv.next - 2 : 0);
-  s = s < len ? s : len;
-  e = e < len ? e : len;
-  e = e > s ? e : s;
-  // T.81 B.1.1.2: 0xFF bytes directly before the interval's RSTm are fill bytes, not data
-  if (!iv.last && iv.next <= len)
-    for (uint64_t i = 0, n = e - s; i < n && a.d.scan[e - 1] == 0xFF; i++)
-      e--;
-  iv.s = s;
-  iv.e = e;
-  iv.mcu0 = k * a.d.restart;
-  const uint32_t nmcu = (a.d.total_mcus - iv.mcu0) < a.d.restart ? a.d.total_mcus - iv.mcu0 : a.d.restart;
-  iv.units = nmcu * a.d.g.upm;
-  return iv;
-}
-
-// lane 0: the interval's status, once its data is judged: the marker after an interval that is not the last must be RST(k mod 8)
-__device__ __forceinline__ void put_status(const ProgArgs &a, const Interval &iv, uint32_t k, uint32_t st)
-{
-  if (st == MDCT_JPEGDEC_OK && !iv.last)
-  {
-    const uint64_t next = iv.next;
-    const bool ok = next >= 2 && next <= a.d.scan_len && next - 2 >= iv.s && a.d.scan[next - 2] == 0xFF && a.d.scan[next - 1] == 0xD0 + (k & 7);
-    if (!ok)
-      st = MDCT_JPEGDEC_UNEXPECTED_MARKER;
-  }
-  a.d.status[k] = st;
 }
 
 // ------------------------------------------------------------------------------------------------------ DC refinement (G.1.2.1)
@@ -393,12 +80,10 @@ __device__ __forceinline__ void refine_dc(const ProgArgs &a, uint32_t *lcomp, in
     *bad = 0;
     *total = 0;
   }
-  const Interval iv = interval_of(a, k);
-  const uint64_t s = iv.s, e = iv.e;
+  const Interval iv = interval_of(a.d, k);
+  const uint64_t s = iv.s, e = iv.e, sb = iv.sb;
   const uint32_t units = iv.units;
   const uint32_t need = units / 8 + 1; // data bytes that matter: one more than the blocks' means bits left over
-  uint64_t sb = (e - s + kThreads - 1) / kThreads;
-  sb = sb < 8 ? 8 : sb;
   uint64_t p0 = s + (uint64_t)tid * sb;
   p0 = p0 < e ? p0 : e;
   const uint64_t p1 = e - p0 > sb ? p0 + sb : e;
@@ -478,7 +163,7 @@ __device__ __forceinline__ void refine_dc(const ProgArgs &a, uint32_t *lcomp, in
     const uint64_t bits = 8ull * *total;
     const uint32_t broken = mlane != kNone ? MDCT_JPEGDEC_UNEXPECTED_MARKER : MDCT_JPEGDEC_OUT_OF_DATA;
     const uint32_t st = bits < units ? broken : (bits - units >= 8 || *bad) ? MDCT_JPEGDEC_LEFTOVER : mlane != kNone ? broken : MDCT_JPEGDEC_OK;
-    put_status(a, iv, k, st);
+    put_status(a.d, iv, k, st);
   }
 }
 
@@ -577,17 +262,12 @@ __device__ __forceinline__ uint64_t from_lane0(uint64_t x)
 
 // One interval of an AC refinement scan by a workgroup of ONE wave (the launch gives it 64 lanes).  Lane i holds zig-zag position i of
 // the current block; the next block's load is in flight while lane 0 decodes.
-__device__ __forceinline__ void refine_ac(const ProgArgs &a, DevTables &T)
+__device__ __forceinline__ void refine_ac(const ProgArgs &a, DevTables &T, uint32_t *lcomp)
 {
   const uint32_t tid = threadIdx.x, k = blockIdx.x;
   const BlockPlace &g = a.d.g;
-  {
-    const uint32_t *src = (const uint32_t *)a.d.tab;
-    uint32_t *dst = (uint32_t *)&T;
-    for (uint32_t i = tid; i < (uint32_t)(sizeof(DevTables) / 4); i += 64)
-      dst[i] = src[i];
-  }
-  const Interval iv = interval_of(a, k);
+  load_tables(a.d, T, lcomp, (int)tid, 64);
+  const Interval iv = interval_of(a.d, k);
   wg_sync();
   const uint32_t comp = g.bcomp[0], units = iv.units;
   const int p1 = 1 << a.al;
@@ -638,7 +318,7 @@ __device__ __forceinline__ void refine_ac(const ProgArgs &a, DevTables &T)
     coef = coming;
   }
   if (tid == 0)
-    put_status(a, iv, k, st ? st : units ? after_last_block(r) : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);
+    put_status(a.d, iv, k, st ? st : units ? after_last_block(r) : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);
 }
 
 template <bool AC>
@@ -647,28 +327,27 @@ __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T,
 {
   const int tid = threadIdx.x;
   const uint32_t k = blockIdx.x;
+  const Band<AC> gr{a.ss, a.se, a.al};
   load_tables(a.d, T, lcomp, tid);
   if (tid == 0)
   {
     *first_err = kNone;
     *fin_word = kNone;
   }
-  const Interval iv = interval_of(a, k);
-  const uint64_t s = iv.s, e = iv.e;
-  const uint64_t sb = (e - s + kThreads - 1) / kThreads;
-  const SubLane q = sub_lane(s, e, sb < 8 ? 8 : sb, tid, true);
+  const Interval iv = interval_of(a.d, k);
+  const SubLane q = sub_lane(iv.s, iv.e, iv.sb, tid, true);
   const uint32_t mcu0 = iv.mcu0, units = iv.units;
   wg_sync();
 
   // ---- synchronisation: lane 0 starts exact (the band's first position of an MCU's first block), the others from the same guess
-  PLane L;
+  Lane L;
   const uint32_t want0 = a.ss << 4;
   uint32_t my_start = want0;
-  speculate<AC>(a, T, lcomp, q, my_start, L);
-  settle<AC>(a, T, lcomp, q, want0, my_start, L, exit_state);
+  speculate(a.d, gr, T, lcomp, q, my_start, L);
+  settle(a.d, gr, T, lcomp, q, want0, my_start, L, exit_state);
 
   // ---- blocks before each lane's start, and the DC predictors there
-  const uint32_t unit0 = first_unit(L.blocks, units, wtot);
+  const uint32_t unit0 = first_unit((uint32_t)L.blocks, units, wtot);
   int pred[3] = {0, 0, 0};
   if (!AC)
     for (int c = 0; c < 3; c++)
@@ -677,7 +356,7 @@ __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T,
   // ---- the decode proper
   uint32_t stop = 0;
   if (q.active)
-    stop = write_pass<AC>(a, T, lcomp, q, my_start, unit0, units, mcu0, pred, first_err, fin_word);
+    stop = write_pass(a.d, gr, T, lcomp, q, my_start, unit0, units, mcu0, pred, first_err, fin_word);
   wg_sync();
   if (*first_err != kNone)
   {
@@ -700,7 +379,7 @@ __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T,
   if (tid == 0)
   {
     const uint32_t st = *first_err != kNone ? (*first_err & 0xFF) : (*fin_word != kNone ? *fin_word : (uint32_t)MDCT_JPEGDEC_OUT_OF_DATA);
-    put_status(a, iv, k, st);
+    put_status(a.d, iv, k, st);
   }
 }
 
@@ -715,7 +394,7 @@ __device__ __forceinline__ void decode_interval(const ProgArgs &a, DevTables &T,
     if (a.ah) /* a refinement scan (uniform) */                                                                                           \
     {                                                                                                                                     \
       if (AC)                                                                                                                             \
-        refine_ac(a, T);                                                                                                                  \
+        refine_ac(a, T, lcomp);                                                                                                           \
       else                                                                                                                                \
         refine_dc(a, lcomp, wtot, &first_err, &fin_word, &fail_unit);                                                                     \
       return;                                                                                                                             \

@@ -116,8 +116,8 @@ __global__ void __launch_bounds__(kThreads) k_um_sync(UmArgs a)
   wg_sync();
   Lane L;
   uint32_t my_start = 0;
-  speculate(a.d, T, lcomp, q, my_start, L);
-  settle(a.d, T, lcomp, q, 0u, my_start, L, exit_state); // lane 0 keeps its start: exact in chunk 0, the guess elsewhere
+  speculate(a.d, Sequential(), T, lcomp, q, my_start, L);
+  settle(a.d, Sequential(), T, lcomp, q, 0u, my_start, L, exit_state); // lane 0 keeps its start: exact in chunk 0, the guess elsewhere
   store_lane(a, (uint64_t)c * kThreads + tid, my_start, L, q.active);
   chunk_totals(a, c, L, q.active, tot);
   if (tid == 0)
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(kThreads) k_um_round(UmArgs a, uint32_t rnd)
     L.dc[k] = a.dc[(size_t)k * a.nlanes + g];
   const uint32_t old_exit = a.exit_[g_last];
   wg_sync();
-  if (settle(a.d, T, lcomp, q, want0, my_start, L, exit_state))
+  if (settle(a.d, Sequential(), T, lcomp, q, want0, my_start, L, exit_state))
     store_lane(a, g, my_start, L, q.active);
   chunk_totals(a, c, L, q.active, tot);
   if (tid == 0)
@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(kThreads) k_um_write(UmArgs a)
     pred[k] = a.cbase[(size_t)(1 + k) * a.nchunks + c] + wg_excl_scan(q.active ? a.dc[(size_t)k * a.nlanes + g] : 0, wtot);
   uint32_t stop = 0;
   if (q.active) // (one lane of the whole scan completes its last block and writes kFin)
-    stop = write_pass(a.d, T, lcomp, q, a.start[g], unit0, a.units, 0, pred, &first_err, &a.ctl[kFin]);
+    stop = write_pass(a.d, Sequential(), T, lcomp, q, a.start[g], unit0, a.units, 0, pred, &first_err, &a.ctl[kFin]);
   wg_sync();
   const uint32_t fe = first_err;
   if (fe != kNone && (uint32_t)tid == fe >> 8)

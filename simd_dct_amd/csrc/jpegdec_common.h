@@ -1,9 +1,11 @@
 // jpegdec_common.h -- what the JPEG decoder libraries share (jpeg_decode.hip: restart-marked scans, libmdct_jpegdec.so;
 // jpeg_decode_unmarked.hip: scans without restart markers, libmdct_jpegdec_unmarked.so; jpeg_decode_batch.hip: the restart-marked scans
 // of many files in one grid, libmdct_jpegdec_batch.so, which runs decode_interval and the index passes below as jpeg_decode.hip
-// does): the device Huffman tables and the handle that owns them (huff_tables.h), the block layout (block_place.h), the bit reader with its unstuffing, the Huffman lookup, the
-// sub-sequence decoder `run`, the skeleton both decoders hang it in -- a lane's sub-sequence (SubLane), the speculative first pass, the
-// settle loop that synchronises the lanes of a workgroup, the write pass -- the workgroup prefix sums and the host's descriptor checks.
+// does; jpeg_decode_progressive.hip: the scans of a progressive file, libmdct_jpegdec_prog.so): the device Huffman tables and the handle
+// that owns them (huff_tables.h), the block layout (block_place.h), the bit reader with its unstuffing, the Huffman lookup, the scan
+// grammars (Sequential: baseline; Band<AC>: a progressive first scan), the one sub-sequence decoder `run` over them, the skeleton every
+// decoder hangs it in -- a lane's sub-sequence (SubLane), the speculative first pass, the settle loop that synchronises the lanes of a
+// workgroup, the write pass -- an interval's bookkeeping (interval_of, put_status), the prefix sums and the host's descriptor checks.
 // Each library includes it from exactly one translation unit; everything here has internal linkage or is a device function.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +28,7 @@ namespace jpegdec
 constexpr int kThreads = 256;   // lanes per restart interval
 constexpr uint32_t kErr = 0x80000000u;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kMaxCount = 0x7FFFFFFFu; // where a lane's block count saturates (a garbage EOBn adds up to 32767 per symbol)
 
 struct DecArgs
 {
@@ -166,11 +169,37 @@ __device__ __forceinline__ int huff(Reader &r, const DevTables &T, int t)
 struct Lane
 {
   uint32_t state;    // packed start / exit state: kErr | d << 12 | k << 4 | b
-  int blocks;        // blocks completed
+  int blocks;        // blocks completed (a Band grammar: end-of-band runs included, saturating at kMaxCount)
   int dc[3];         // sum of the DC differences per component
   uint32_t err;      // MDCT_JPEGDEC_* of a decode error (final pass)
   bool finished;     // completed the interval's last block (final pass)
   uint32_t fin;      // status after the last block: OK / LEFTOVER / UNEXPECTED_MARKER
+};
+
+// ------------------------------------------------------------------------------------------------------------------ the scan grammars
+// What `run` decodes.  Sequential: a baseline scan (T.81 F.2.2): per block the DC symbol at k == 0, then AC symbols up to position 63;
+// S = 0 without ZRL ends the block.  Band<AC>: a first scan of a progressive file (G.1.2), levels in units of 1 << al: the DC scan
+// (every symbol a DC symbol) or an AC band ss..se (no DC symbol; S = 0 without ZRL is EOBn, ending (1 << R) + (R extra bits) blocks).
+enum class Scan { Sequential, DcFirst, AcBand };
+struct Sequential
+{
+  static constexpr Scan kind = Scan::Sequential;
+  static constexpr uint32_t ss = 0, se = 63, al = 0;
+};
+
+template <bool AC>
+struct Band // an AC band: one block per MCU (the block in MCU stays 0), and EOBn runs
+{
+  static constexpr Scan kind = Scan::AcBand;
+  uint32_t ss, se, al;
+};
+template <>
+struct Band<false> // the DC scan: its band is 0..0 by definition
+{
+  static constexpr Scan kind = Scan::DcFirst;
+  static constexpr uint32_t ss = 0, se = 0;
+  uint32_t al;
+  __device__ Band(uint32_t, uint32_t, uint32_t al_) : al(al_) {}
 };
 
 __device__ __forceinline__ void reader_init(Reader &r, const DecArgs &a, uint64_t s0, uint64_t end, uint64_t E, bool first)
@@ -199,12 +228,27 @@ __device__ __forceinline__ void reader_init(Reader &r, const DecArgs &a, uint64_
   }
 }
 
+// the interval's last block is complete: what follows must be its padding (1-bits to the byte boundary) and nothing else
+__device__ __forceinline__ uint32_t after_last_block(Reader &r)
+{
+  refill(r);
+  uint32_t fin = MDCT_JPEGDEC_LEFTOVER;
+  if (r.dry)
+  {
+    const uint32_t rem = r.uend - r.u;
+    if (rem < 8 && (rem == 0 || (uint32_t)(r.buf >> (64 - rem)) == (1u << rem) - 1u))
+      fin = r.marker ? MDCT_JPEGDEC_UNEXPECTED_MARKER : MDCT_JPEGDEC_OK;
+  }
+  return fin;
+}
+
 // Decode from state `start` until the first symbol boundary at or after the next sub-sequence's start (a lane with a successor), the
 // interval's last block (WRITE with a unit budget), or an error.  WRITE: unit0 blocks precede the start; pred = DC predictors there.
-template <bool WRITE>
-__device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint32_t *lcomp, uint32_t start, Lane &out, uint32_t unit0,
-                    uint32_t units, uint32_t mcu0, int pred[3], uint64_t cap)
+template <bool WRITE, class G>
+__device__ void run(Reader &r, const DecArgs &a, const G &gr, const DevTables &T, const uint32_t *lcomp, uint32_t start, Lane &out,
+                    uint32_t unit0, uint32_t units, uint32_t mcu0, int pred[3], uint64_t cap)
 {
+  constexpr bool kAcBand = G::kind == Scan::AcBand;
   out.blocks = 0;
   out.dc[0] = out.dc[1] = out.dc[2] = 0;
   out.err = 0;
@@ -249,8 +293,10 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
       out.state = ((r.u - r.uE) << 12) | (k << 4) | b;
       return;
     }
-    bool block_end = false;
-    const int sym = huff(r, T, k == 0 ? a.bdc[b] : a.bac[b]);
+    bool block_end = false; // the symbol completes a block ...
+    uint32_t ended = 1;     // ... and with it this many (an EOBn: the run)
+    const bool dc = G::kind == Scan::DcFirst || (G::kind == Scan::Sequential && k == 0); // a DC symbol comes
+    const int sym = huff(r, T, dc ? a.bdc[b] : a.bac[kAcBand ? 0 : b]);
     if (sym < 0)
     {
       out.err = no_code(r);
@@ -260,10 +306,10 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
       out.err = 0;
       block_end = true;
     }
-    else if (k == 0)
+    else if (dc)
     {
-      const int s = sym;
-      const int diff = extend(get_bits(r, s & 15), s & 15);
+      const uint32_t s = (uint32_t)sym & 15;
+      const int diff = extend(get_bits(r, s), s);
       if (overrun(r))
       {
         out.err = data_error(r);
@@ -273,49 +319,60 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
       if (WRITE)
       {
         pred[comp] += diff;
-        bp[0] = (int16_t)pred[comp];
+        bp[0] = (int16_t)((uint32_t)pred[comp] << gr.al);
       }
       k = 1;
+      block_end = gr.se == 0;
     }
     else
     {
-      const int rs = sym;
       if (overrun(r))
       {
         out.err = data_error(r);
         return;
       }
-      const uint32_t run_ = (uint32_t)rs >> 4, s = (uint32_t)rs & 15;
+      const uint32_t run_ = (uint32_t)sym >> 4, s = (uint32_t)sym & 15;
       if (s == 0)
       {
-        if (run_ == 15)
+        if (run_ == 15) // ZRL
         {
           k += 16;
-          if (k > 64)
+          if (k > gr.se + 1)
           {
             if (WRITE)
             {
               out.err = MDCT_JPEGDEC_COEF_OVERFLOW;
               return;
             }
-            k = 64; // speculating: end the block
+            k = gr.se + 1; // speculating: end the block
           }
-          block_end = k == 64;
+          block_end = k == gr.se + 1;
         }
-        else
-          block_end = true; // EOB
+        else // EOB, EOBn
+        {
+          block_end = true;
+          if constexpr (kAcBand)
+          {
+            ended = (1u << run_) + get_bits(r, run_);
+            if (overrun(r))
+            {
+              out.err = data_error(r);
+              return;
+            }
+          }
+        }
       }
       else
       {
         k += run_;
-        if (k > 63)
+        if (k > gr.se)
         {
           if (WRITE)
           {
             out.err = MDCT_JPEGDEC_COEF_OVERFLOW;
             return;
           }
-          k = 63; // speculating: keep the bit position, end the block after this level
+          k = gr.se; // speculating: keep the bit position, end the block after this level
         }
         const int v = extend(get_bits(r, s), s);
         if (overrun(r))
@@ -326,37 +383,48 @@ __device__ void run(Reader &r, const DecArgs &a, const DevTables &T, const uint3
         if (WRITE)
         {
           const uint32_t z = kZigzag[k];
-          bp[(size_t)(z >> 3) * a.g.pitch[comp] + (z & 7)] = (int16_t)v;
+          bp[(size_t)(z >> 3) * a.g.pitch[comp] + (z & 7)] = (int16_t)((uint32_t)v << gr.al);
         }
         k++;
-        block_end = k == 64;
+        block_end = k == gr.se + 1;
       }
     }
     if (block_end)
     {
-      k = 0;
-      out.blocks++;
-      if (++b == a.g.upm)
-        b = 0;
-      comp = lcomp[b];
-      if (WRITE)
+      k = gr.ss;
+      if constexpr (kAcBand)
       {
-        if (++unit == units)
+        if (WRITE && ended > units - unit) // unit < units here; the block of the EOBn is the failing one
         {
-          // the interval's last block: what follows must be its padding (1-bits to the byte boundary) and nothing else
-          out.finished = true;
-          refill(r);
-          uint32_t fin = MDCT_JPEGDEC_LEFTOVER;
-          if (r.dry)
-          {
-            const uint32_t rem = r.uend - r.u;
-            if (rem < 8 && (rem == 0 || (uint32_t)(r.buf >> (64 - rem)) == (1u << rem) - 1u))
-              fin = r.marker ? MDCT_JPEGDEC_UNEXPECTED_MARKER : MDCT_JPEGDEC_OK;
-          }
-          out.fin = fin;
+          out.err = MDCT_JPEGDEC_EOBRUN_OVERFLOW;
           return;
         }
-        if (b == 0 && ++mx == a.g.mcus_x)
+        out.blocks = (int)((uint32_t)out.blocks + ended < kMaxCount ? (uint32_t)out.blocks + ended : kMaxCount);
+      }
+      else
+        out.blocks++;
+      if constexpr (!kAcBand)
+      {
+        if (++b == a.g.upm)
+          b = 0;
+        comp = lcomp[b];
+      }
+      if (WRITE)
+      {
+        unit += ended;
+        if (unit == units)
+        {
+          out.finished = true;
+          out.fin = after_last_block(r);
+          return;
+        }
+        if (kAcBand && ended > 1) // a run is an AC band's, one block per MCU: over its blocks
+        {
+          const uint32_t mcu = mcu0 + unit;
+          my = mcu / a.g.mcus_x;
+          mx = mcu - my * a.g.mcus_x;
+        }
+        else if (b == 0 && ++mx == a.g.mcus_x)
         {
           mx = 0;
           my++;
@@ -443,20 +511,22 @@ __device__ __forceinline__ SubLane sub_lane(uint64_t s, uint64_t end, uint64_t s
   return q;
 }
 
-// the tables and the blocks' components into LDS (lcomp: 16 words); the caller synchronises
-__device__ __forceinline__ void load_tables(const DecArgs &a, DevTables &T, uint32_t *lcomp, int tid)
+// the tables and the blocks' components into LDS (lcomp: 16 words) by a workgroup of `lanes` lanes; the caller synchronises
+__device__ __forceinline__ void load_tables(const DecArgs &a, DevTables &T, uint32_t *lcomp, int tid, int lanes = kThreads)
 {
   const uint32_t *src = (const uint32_t *)a.tab;
   uint32_t *dst = (uint32_t *)&T;
-  for (int i = tid; i < (int)(sizeof(DevTables) / 4); i += kThreads)
+  for (int i = tid; i < (int)(sizeof(DevTables) / 4); i += lanes)
     dst[i] = src[i];
   if (tid < 16)
     lcomp[tid] = tid < (int)a.g.upm ? a.g.bcomp[tid] : 0;
 }
 
 // One speculating decode of the lane's sub-sequence from state `start`; a lane without data publishes no usable exit, no blocks, no DC.
-// The first pass starts every lane from 0: bit 0 of its first byte, the DC code of an MCU's first block.
-__device__ __forceinline__ void speculate(const DecArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t start, Lane &L)
+// The first pass starts every lane from the same guess: bit 0 of its first byte, the first position (ss) of an MCU's first block.
+template <class G>
+__device__ __forceinline__ void speculate(const DecArgs &a, const G &gr, const DevTables &T, const uint32_t *lcomp, const SubLane &q,
+                                          uint32_t start, Lane &L)
 {
   Reader r;
   int dummy[3] = {0, 0, 0};
@@ -465,14 +535,15 @@ __device__ __forceinline__ void speculate(const DecArgs &a, const DevTables &T, 
   if (!q.active)
     return;
   reader_init(r, a, q.s0, q.end, q.E, q.first);
-  run<false>(r, a, T, lcomp, start, L, 0, 0, 0, dummy, q.cap);
+  run<false>(r, a, gr, T, lcomp, start, L, 0, 0, 0, dummy, q.cap);
 }
 
 // The synchronisation inside a workgroup: lane 0 wants want0, lane i the exit of lane i - 1; a lane whose start differs decodes again,
 // until no start changes (at most nact + 1 trips: each trip makes one more lane exact).  exit_state: kThreads words of LDS, every
 // lane's exit state on return.  Returns whether this lane decoded again.
-__device__ __forceinline__ bool settle(const DecArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t want0,
-                                       uint32_t &my_start, Lane &L, uint32_t *exit_state)
+template <class G>
+__device__ __forceinline__ bool settle(const DecArgs &a, const G &gr, const DevTables &T, const uint32_t *lcomp, const SubLane &q,
+                                       uint32_t want0, uint32_t &my_start, Lane &L, uint32_t *exit_state)
 {
   bool ran = false;
   exit_state[threadIdx.x] = L.state;
@@ -487,7 +558,7 @@ __device__ __forceinline__ bool settle(const DecArgs &a, const DevTables &T, con
     if (changed)
     {
       my_start = want;
-      speculate(a, T, lcomp, q, my_start, L);
+      speculate(a, gr, T, lcomp, q, my_start, L);
       exit_state[threadIdx.x] = L.state;
       ran = true;
     }
@@ -499,13 +570,15 @@ __device__ __forceinline__ bool settle(const DecArgs &a, const DevTables &T, con
 // The write pass of a lane with data: the exact decode from `start`, unit0 blocks and the predictors `pred` before it, writing levels.
 // A decode error goes to *first_err (LDS, kNone before) as lane << 8 | code, the smallest winning; the status after the range's last
 // block to *fin.  Returns the unit the lane stopped in (unit0 + the blocks it completed): the failing one in the lane that wins.
-__device__ __forceinline__ uint32_t write_pass(const DecArgs &a, const DevTables &T, const uint32_t *lcomp, const SubLane &q, uint32_t start,
-                                               uint32_t unit0, uint32_t units, uint32_t mcu0, int pred[3], uint32_t *first_err, uint32_t *fin)
+template <class G>
+__device__ __forceinline__ uint32_t write_pass(const DecArgs &a, const G &gr, const DevTables &T, const uint32_t *lcomp, const SubLane &q,
+                                               uint32_t start, uint32_t unit0, uint32_t units, uint32_t mcu0, int pred[3],
+                                               uint32_t *first_err, uint32_t *fin)
 {
   Reader r;
   Lane F;
   reader_init(r, a, q.s0, q.end, q.E, q.first);
-  run<true>(r, a, T, lcomp, start, F, unit0, units, mcu0, pred, q.cap);
+  run<true>(r, a, gr, T, lcomp, start, F, unit0, units, mcu0, pred, q.cap);
   if (F.err && unit0 < units)
     atomicMin(first_err, ((uint32_t)threadIdx.x << 8) | F.err);
   if (F.finished)
@@ -514,9 +587,56 @@ __device__ __forceinline__ uint32_t write_pass(const DecArgs &a, const DevTables
 }
 
 // ------------------------------------------------------------------------------------------------------------------ one restart interval
-// The whole of k_decode (jpeg_decode.hip) for interval k of the scan `a` describes, run by one workgroup of kThreads lanes; k_decode_batch
-// (jpeg_decode_batch.hip) calls it with a scan record it looked up and the interval's index within that scan.  Everything that depends
-// on the interval's number -- its first MCU, RST(k mod 8), the `last` flag, off[k] / off[k + 1], status[k] -- is taken from k.
+// Interval k of the scan `a` describes, for the progressive scans (jpeg_decode_progressive.hip).  decode_interval below holds the same
+// statements in line, and a change to one goes into the other: taken from here, k_decode was 1.5-2 % slower.
+struct Interval
+{
+  uint64_t s, e, next;  // its data [s, e), clamped into the scan whatever the offsets say; off[k + 1] as given
+  uint64_t sb;          // bytes per lane's sub-sequence when one workgroup of kThreads lanes decodes it
+  bool last;
+  uint32_t mcu0, units; // its first MCU, its blocks
+};
+
+__device__ __forceinline__ Interval interval_of(const DecArgs &a, const uint32_t k)
+{
+  Interval iv;
+  const uint64_t len = a.scan_len;
+  iv.last = k + 1 == a.n_intervals;
+  uint64_t s = a.off[k];
+  iv.next = a.off[k + 1];
+  uint64_t e = iv.last ? iv.next : (iv.next >= 2 ? iv.next - 2 : 0);
+  s = s < len ? s : len;
+  e = e < len ? e : len;
+  e = e > s ? e : s;
+  // T.81 B.1.1.2: 0xFF bytes directly before the interval's RSTm are fill bytes, not data
+  if (!iv.last && iv.next <= len)
+    for (uint64_t i = 0, n = e - s; i < n && a.scan[e - 1] == 0xFF; i++)
+      e--;
+  iv.s = s;
+  iv.e = e;
+  const uint64_t sb = (e - s + kThreads - 1) / kThreads;
+  iv.sb = sb < 8 ? 8 : sb;
+  iv.mcu0 = k * a.restart;
+  const uint32_t nmcu = (a.total_mcus - iv.mcu0) < a.restart ? a.total_mcus - iv.mcu0 : a.restart;
+  iv.units = nmcu * a.g.upm;
+  return iv;
+}
+
+// lane 0: the interval's status, once its data is judged: the marker after an interval that is not the last must be RST(k mod 8)
+__device__ __forceinline__ void put_status(const DecArgs &a, const Interval &iv, const uint32_t k, uint32_t st)
+{
+  if (st == MDCT_JPEGDEC_OK && !iv.last)
+  {
+    const uint64_t next = iv.next;
+    const bool ok = next >= 2 && next <= a.scan_len && next - 2 >= iv.s && a.scan[next - 2] == 0xFF && a.scan[next - 1] == 0xD0 + (k & 7);
+    if (!ok)
+      st = MDCT_JPEGDEC_UNEXPECTED_MARKER;
+  }
+  a.status[k] = st;
+}
+
+// The whole of k_decode (jpeg_decode.hip) for interval k, run by one workgroup of kThreads lanes; k_decode_batch (jpeg_decode_batch.hip)
+// calls it with a scan record it looked up and the interval's index within that scan.
 __device__ __forceinline__ void decode_interval(const DecArgs &a, const uint32_t k)
 {
   __shared__ DevTables T;
@@ -525,6 +645,7 @@ __device__ __forceinline__ void decode_interval(const DecArgs &a, const uint32_t
   __shared__ int wtot[kThreads / 64];
   __shared__ uint32_t first_err, fin_word, fail_unit;
   const int tid = threadIdx.x;
+  const Sequential gr;
   load_tables(a, T, lcomp, tid);
   if (tid == 0)
   {
@@ -555,8 +676,8 @@ __device__ __forceinline__ void decode_interval(const DecArgs &a, const uint32_t
   // ---- synchronisation: lane 0 starts exact, the others from a guess, until no start changes
   Lane L;
   uint32_t my_start = 0;
-  speculate(a, T, lcomp, q, my_start, L);
-  settle(a, T, lcomp, q, 0u, my_start, L, exit_state);
+  speculate(a, gr, T, lcomp, q, my_start, L);
+  settle(a, gr, T, lcomp, q, 0u, my_start, L, exit_state);
 
   // ---- blocks before each lane's start, and the DC predictors there (an idle lane counts nothing)
   const uint32_t unit0 = (uint32_t)wg_excl_scan(L.blocks, wtot);
@@ -574,7 +695,7 @@ __device__ __forceinline__ void decode_interval(const DecArgs &a, const uint32_t
   // ---- the decode proper
   uint32_t stop = 0;
   if (q.active)
-    stop = write_pass(a, T, lcomp, q, my_start, unit0, units, mcu0, pred, &first_err, &fin_word);
+    stop = write_pass(a, gr, T, lcomp, q, my_start, unit0, units, mcu0, pred, &first_err, &fin_word);
   wg_sync();
   if (first_err != kNone)
   {

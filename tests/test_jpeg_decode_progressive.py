@@ -509,7 +509,7 @@ def dc_check(torch, p, gx, gy, R=None):
 def test_one_plane_scans_at_the_seams_of_256_lanes(gpu, width):
     rng = np.random.default_rng(width)
     p = sparse(rng, (16, width * 8), density=0.08)
-    for ss, se in ((1, 63), (6, 63), (1, 5), (7, 7)):
+    for ss, se in ((1, 63), (6, 63), (1, 5), (7, 7), (63, 63)):  # (63, 63): se + 1 == 64, where a baseline block ends
         ac_check(gpu, p, width, 2, ss, se)
     dc_check(gpu, p, width, 2)
 
