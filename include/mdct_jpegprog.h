@@ -1,6 +1,6 @@
-/* mdct_jpegprog.h -- C-ABI of libmdct_jpegprog.so: the scans of a progressive JPEG (SOF2) with spectral selection, Ah = Al = 0
- * (ITU-T T.81 Annex G.1.2), coded from quantised coefficient planes: one DC scan, then scans of one band Ss..Se of one component with
- * end-of-band runs.  Successive approximation (refinement scans) is out of scope.  libmdct_jpegdec_prog.so
+/* mdct_jpegprog.h -- C-ABI of libmdct_jpegprog.so: the scans of a progressive JPEG (SOF2), spectral selection and successive
+ * approximation (ITU-T T.81 Annex G.1.2), coded from quantised coefficient planes: DC scans, and scans of one band Ss..Se of one
+ * component with end-of-band runs; first scans and refinement scans (the ..._approx calls below).  libmdct_jpegdec_prog.so
  * (include/mdct_jpegdec_prog.h) decodes these scans back into the planes.
  *
  * A separate library, linked against libmdct_hip.so (include/mdct.h: status codes, launch tally, the packing call) and
@@ -61,6 +61,43 @@ int mdct_jpegprog_ac_stats(const mdct_jpegcoef_plane *plane, int ss, int se, uin
  * 0x10 .. 0xE0 are the EOBn of this scan).  uncoded as above. */
 int mdct_jpegprog_ac_rows(const mdct_jpegcoef_plane *plane, int ss, int se, size_t by0, size_t by1, const mdct_jpegenc_opt_spec *ac, uint8_t *out, size_t seg_stride,
                           uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream);
+
+/* Successive approximation (G.1.2): the four calls above with the scan's Ah and Al; with ah = al = 0 they write what those write.
+ * Refused on the host (MDCT_INVALID_PARAMETER): al outside 0..13, and ah not in {0, al + 1}.
+ *
+ * DC first, al > 0 (encode_mcu_DC_first): the differences of dc >> al, an arithmetic shift; differences of the shifted values outside
+ * +-2047 are counted as above.
+ * DC refinement, ah = al + 1 (dc_rows_approx only; dc_stats_approx refuses ah != 0, there are no symbols): one raw bit
+ * (dc >> al) & 1 per block in scan order, padded with 1-bits; no table (specs may be NULL), nothing is added to *uncoded or
+ * *unrepresentable.  One plane with an interval per block row, or three in MCU order with an interval per MCU row, as the first scan.
+ *
+ * AC first, al > 0 (encode_mcu_AC_first): the level is |v| >> al with v's sign; a level that becomes 0 counts as a zero, for runs and
+ * for the tail flag alike.
+ * AC refinement, ah = al + 1 (encode_mcu_AC_refine, exactly).  Let a[k] = |v[k]| >> al and EOB the last k of the band with a[k] == 1.
+ * Walking k = ss..se: a == 0 counts a zero, r++.  At a non-zero position, first: while r > 15 and k <= EOB, flush the pending run
+ * with its buffered bits, emit ZRL and then the block's buffered correction bits, r -= 16.  a > 1: buffer the correction bit a & 1.
+ * a == 1: flush the pending run with its bits, emit (r << 4) | 1, a sign bit (1: positive) and the block's buffered correction bits;
+ * r = 0.  After the block: if r > 0 or bits are buffered, the run grows by one and takes the block's bits; it is flushed at once when
+ * it reaches 0x7FFF or holds more than 937 bits, and at the end of every interval.  A flush emits EOBn (none for a run of 0), its n
+ * extra bits, then the buffered bits in order.  hist: exactly the symbols emitted.
+ *
+ * Clamping: an AC level is clamped to +-1023 BEFORE the point transform in every AC scan kind, so all scans of one coefficient agree;
+ * a clamped level is counted in *unrepresentable by the first scan of its band only (ah = 0), never by a refinement scan.
+ *
+ * seg_stride: mdct_jpegenc_opt_seg_stride still bounds a segment.  DC scans: at most 27 bits, or one bit, per block.  AC refinement:
+ * charge every bit to the block whose coefficient it codes, buffered or not.  A position of the band gives its block at most 17 bits
+ * -- a == 1: a code of at most 16 bits and the sign bit; a > 1: one correction bit; a == 0: at most 1/16 of a ZRL of 16 bits -- so a
+ * block owns at most 63 * 17 = 1071 bits wherever in the segment they end up.  Every EOBn token (at most 16 + 14 bits) is emitted
+ * for a run that begins at some tail block, and a block begins at most one run: charged to that block, 1101 bits in all, below the
+ * 1672 of 209 bytes.  Nothing is emitted that is charged to no block, so an interval of n blocks holds at most 1101 n bits; the
+ * padded last dword fits in the 8 bytes.  An AC first scan with al > 0 emits the symbols of an al = 0 scan of the shifted levels. */
+int mdct_jpegprog_dc_stats_approx(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, int cls, int ah, int al, uint32_t *hist, uint32_t *unrepresentable,
+                                  void *stream);
+int mdct_jpegprog_dc_rows_approx(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, const mdct_jpegenc_opt_spec *specs, int ah, int al, size_t r0, size_t r1,
+                                 uint8_t *out, size_t seg_stride, uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream);
+int mdct_jpegprog_ac_stats_approx(const mdct_jpegcoef_plane *plane, int ss, int se, int ah, int al, uint32_t *hist, uint32_t *unrepresentable, void *stream);
+int mdct_jpegprog_ac_rows_approx(const mdct_jpegcoef_plane *plane, int ss, int se, int ah, int al, size_t by0, size_t by1, const mdct_jpegenc_opt_spec *ac, uint8_t *out,
+                                 size_t seg_stride, uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream);
 
 /* detail of the last failure of this library on any thread (host function) */
 const char *mdct_jpegprog_last_error(void);

@@ -1,6 +1,6 @@
-// jpeg_progressive.hip -- the scans of a progressive JPEG with spectral selection, Ah = Al = 0 (include/mdct_jpegprog.h; ITU-T T.81
-// Annex G.1.2): quantised coefficient planes -> the Huffman segments of the DC-first scan and of the scans of
-// one AC band of one component with end-of-band runs, and their symbol statistics.
+// jpeg_progressive.hip -- the scans of a progressive JPEG, spectral selection and successive approximation (include/mdct_jpegprog.h;
+// ITU-T T.81 Annex G.1.2; DESIGN.md sections 4.12 and 4.12.1): quantised coefficient planes -> the segments of DC scans and of the scans
+// of one AC band of one component with end-of-band runs, first scans and refinement scans, and their symbol statistics.
 //
 // Built into its own library, libmdct_jpegprog.so, linked against libmdct_hip.so (launch tally) and libmdct_jpegenc_opt.so (segment
 // stride).
@@ -8,7 +8,11 @@
 // k_prog_dc<H, V, STATS> is k_coef (jpeg_coef.hip) with a source that fetches the DC level alone: the kernel body is opt_symbols.h's
 // with no AC entries and no EOB (HuffSeqCoder16::chunk with n = 0), the lane-to-block layout scan_chunks.h's ChunkGrid.
 //
-// k_prog_ac<STATS>: one workgroup of 4 waves per block row, chunks of 256 blocks, lane = block in both phases.
+// k_prog_dc<H, V, false> with DcArgs' refine set is the DC refinement scan instead (dc_refine: one raw bit per block).
+//
+// k_prog_ac<STATS> branches, uniformly, into a first scan without or with a point transform (band_first) and a refinement scan
+// (band_refine, described there); the kernels' names and number are those of the Ah = Al = 0 library.  A first scan:
+// one workgroup of 4 waves per block row, chunks of 256 blocks, lane = block in both phases.
 //   fetch    the lane's 8 rows (the fetch of CoefChunks), the levels of zig-zag positions ss..se compacted into its LDS row as
 //            run << 12 | level entries; zeros outside the band are not counted and levels outside it do not appear.  Two flags per
 //            block: non-empty (an entry) and tail (position se is zero); each wave leaves its two 64-bit ballots in LDS.
@@ -55,6 +59,8 @@ struct DcArgs
   uint32_t mcus_x, my0;
   uint32_t cls0;       // one plane: its class in the histogram
   uint32_t complete;   // coder: every DC category has a code
+  uint32_t al;         // the point transform: the scan codes dc >> al (arithmetic)
+  uint32_t refine;     // coder: the refinement scan -- bit al of every DC, no table (dc_refine below)
   uint32_t dc[2][12];  // size << 16 | code per DC category, 0: no code; one plane: its table in [0]
   uint32_t ac[2][256]; // all zero: the body's AC tables, never looked up
 };
@@ -80,7 +86,7 @@ struct DcChunks : ChunkGrid<H, V, Args>
 
   __device__ __forceinline__ explicit DcChunks(const Args &a_) : Grid(a_) {}
 
-  __device__ __forceinline__ void fetch(uint32_t bx) { level = src_row[(size_t)min(bx, last_blk) * 8]; }
+  __device__ __forceinline__ void fetch(uint32_t bx) { level = (int16_t)(src_row[(size_t)min(bx, last_blk) * 8] >> a.al); }
 
   __device__ __forceinline__ void init(uint32_t tid_, uint32_t lane, uint32_t wave, uint32_t my, uint16_t *rec_all, uint32_t (*meta_)[Grid::kThreads])
   {
@@ -102,12 +108,6 @@ struct DcChunks : ChunkGrid<H, V, Args>
   }
 };
 
-template <int H, int V, bool STATS>
-__global__ __launch_bounds__((64 * kWaves<H, V>)) void k_prog_dc(DcArgs a)
-{
-  opt_symbols::opt_kernel_body<DcChunks<H, V, DcArgs>, H, V, STATS>(a);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------- an AC band
 struct BandArgs
 {
@@ -121,6 +121,7 @@ struct BandArgs
   uint32_t blocks_x, by0;
   uint32_t ss, se;
   uint32_t complete; // coder: every symbol of a band scan has a code
+  uint32_t ah, al;   // successive approximation: ah = 0, a first scan of |v| >> al with v's sign; ah = al + 1, the refinement scan of bit al of |v|
   uint32_t ac[256];  // size << 16 | code per RRRRSSSS, 0: no code
 };
 static_assert(sizeof(BandArgs) <= 4096, "kernel argument block");
@@ -282,16 +283,37 @@ struct BandCoder : HuffSeqCoder16<(int)kBandWaves, kRing>
   }
 };
 
+constexpr uint32_t kBufWords = 32; // the buffer of a refinement scan's open run: 1024 bits >= 937 + 63
+
+// the LDS of k_prog_ac<STATS>, one set for the scan kinds it branches into
 template <bool STATS>
-__global__ __launch_bounds__(kBandThreads) void k_prog_ac(BandArgs a)
+struct BandLds
 {
-  __shared__ uint32_t ac[STATS ? 1 : 256];
-  __shared__ __attribute__((aligned(16))) uint16_t rec_all[kBandThreads * kRec16Row];
-  __shared__ unsigned long long ne[kBandWaves], tl[kBandWaves]; // the waves' ballots of non-empty and of tail blocks
-  __shared__ uint32_t ring[STATS ? 1 : kRing];
-  __shared__ uint32_t tot[2][kBandWaves];
-  __shared__ uint32_t ff_total;
-  __shared__ uint32_t hist[STATS ? kBandWaves : 1][STATS ? 256 : 1]; // one histogram per wave
+  __attribute__((aligned(16))) uint16_t rec_all[kBandThreads * kRec16Row];
+  uint32_t ac[STATS ? 1 : 256];
+  unsigned long long ne[kBandWaves], tl[kBandWaves]; // the waves' ballots of non-empty and of tail blocks
+  uint32_t ring[STATS ? 1 : kRing];
+  uint32_t tot[2][kBandWaves];
+  uint32_t ff_total;
+  uint32_t hist[STATS ? kBandWaves : 1][STATS ? 256 : 1]; // one histogram per wave
+  // a refinement scan only
+  uint32_t info[kBandThreads];                        // non-empty | tail << 1 | tail bits << 2
+  uint32_t buf[STATS ? 1 : 2][STATS ? 1 : kBufWords]; // the tail bits of the open run, MSB first; the other one is clear
+};
+
+// A first scan (Ah = 0).  SHIFT: Al > 0 -- the level is |v| >> al with v's sign (clamped first); a level that becomes 0 is a zero for
+// runs and tail flag alike
+template <bool STATS, bool SHIFT>
+__device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &lds)
+{
+  auto &ac = lds.ac;
+  auto &rec_all = lds.rec_all;
+  auto &ne = lds.ne;
+  auto &tl = lds.tl;
+  auto &ring = lds.ring;
+  auto &tot = lds.tot;
+  auto &ff_total = lds.ff_total;
+  auto &hist = lds.hist;
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t by = a.by0 + blockIdx.x;
@@ -352,9 +374,14 @@ __global__ __launch_bounds__(kBandThreads) void k_prog_ac(BandArgs a)
     {
       const bool in = (uint32_t)k >= ss && (uint32_t)k <= se;
       const int l = val[kZigZag[k]];
-      const int c = l > 1023 ? 1023 : (l < -1023 ? -1023 : l);
-      const bool nz = in && l != 0;
+      int c = l > 1023 ? 1023 : (l < -1023 ? -1023 : l);
       clamped += (in && c != l) ? 1u : 0u;
+      if constexpr (SHIFT)
+      {
+        const int mag = (c < 0 ? -c : c) >> a.al;
+        c = c < 0 ? -mag : mag;
+      }
+      const bool nz = in && c != 0;
       const bool wr = nz || (in && r12 == 0xF000u);
       rec[pos] = (uint16_t)(((uint32_t)c & 0xFFFu) | r12);
       pos += wr ? 1u : 0u;
@@ -468,6 +495,532 @@ __global__ __launch_bounds__(kBandThreads) void k_prog_ac(BandArgs a)
   }
 }
 
+// ------------------------------------------------------------------------------------------------------- an AC refinement scan
+// band_refine<STATS>, the Ah != 0 branch of k_prog_ac: libjpeg's encode_mcu_AC_refine in the first scan's shape -- one workgroup of 4 waves per block row, chunks of 256
+// blocks, lane = block.  With a[k] = min(|v[k]|, 1023) >> al and EOB the last position of the band with a == 1, a block is
+//   content  (only if some a == 1: the block is NON-EMPTY) per a == 1 the symbol r << 4 | 1 and a sign bit, and a ZRL at the 16th zero
+//            in a row in front of EOB; behind either, the correction bits (a & 1 of the positions with a > 1) gathered since the last one;
+//   tail     the correction bits behind EOB; the block is a TAIL block if any position follows EOB (always, if it is empty).
+// A run is a stretch of tail blocks: it begins at a tail block (the only one that may be non-empty) and ends in front of the next
+// non-empty block, behind the block that makes it 0x7FFF long or its tail bits more than 937, or with the interval.  The stream holds
+// a run as EOBn, then the tail bits of its blocks in order, so the lane of the run's FIRST block emits the token once the run's
+// length is known:
+//   closed in this chunk   the length follows from the masks of non-empty and of flushing blocks; content, token and tail bits take
+//                          their places through the scan of the lanes' bit counts;
+//   open at the chunk's end   its tail bits go into an LDS buffer (at most 937 + 63 bits) that is carried with the run's length; the
+//                          chunk that closes it has lane 0 emit the token and the buffer in front of everything else.
+// The flush rule is a running sum with resets: every wave walks the chunk's 256 (non-empty, tail, tail bits) triples, read from LDS
+// into four registers beforehand and taken by v_readlane, in scalar registers alone; it yields the mask of flushing blocks, the
+// state after the chunk and where the run that stays open began.
+constexpr uint32_t kMaxBuffered = 937; // libjpeg's MAX_CORR_BITS - DCTSIZE2 + 1: a run whose buffered bits exceed it is flushed
+constexpr uint32_t kNone = 1024;       // "no such block" of next_block
+
+// the first block >= from whose bit is set in the four 64-bit masks, or kNone
+__device__ __forceinline__ uint32_t next_block(unsigned long long m0, unsigned long long m1, unsigned long long m2, unsigned long long m3, uint32_t from)
+{
+  const unsigned long long m[4] = {m0, m1, m2, m3};
+  uint32_t res = kNone;
+#pragma unroll
+  for (int w = 3; w >= 0; w--)
+  {
+    const int lo = (int)from - w * 64;
+    const unsigned long long x = lo >= 64 ? 0ull : (lo > 0 ? m[w] & (~0ull << lo) : m[w]);
+    if (x)
+      res = (uint32_t)(w * 64 + __builtin_ctzll(x));
+  }
+  return res;
+}
+
+__device__ __forceinline__ bool block_bit(unsigned long long m0, unsigned long long m1, unsigned long long m2, unsigned long long m3, uint32_t i)
+{
+  const uint32_t w = i >> 6;
+  const unsigned long long m = w == 0 ? m0 : w == 1 ? m1 : w == 2 ? m2 : m3;
+  return ((m >> (i & 63)) & 1ull) != 0;
+}
+
+// entries of a refinement block in its LDS row: symbol (r << 4 | 1, or 0xF0) | sign << 8 | correction bits behind it << 9
+__device__ __forceinline__ uint32_t ref_symbol(uint32_t e) { return e & 0xFFu; }
+__device__ __forceinline__ uint32_t ref_ncorr(uint32_t e) { return e >> 9; }
+
+// BandCoder's window loop for a lane whose bits are a sequence only it can replay: emit(put) calls put(bits, len <= 16) in stream
+// order, the same calls every time.  packed = the lane's bit count | the bits it leaves in the carried buffer << 20 (both scanned at
+// once: a chunk holds < 2^19 bits and an open run <= 1000 buffered ones); *buffered_before: the second scan's exclusive prefix.
+struct RefineCoder : BandCoder
+{
+  template <class Emit>
+  __device__ __forceinline__ void chunk_emit(uint32_t packed, bool live, uint32_t *buffered_before, uint32_t *buffered_total, Emit emit)
+  {
+    constexpr uint32_t RING = kRing;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t incl = packed;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+    {
+      const uint32_t v = __shfl_up(incl, d, 64);
+      if (lane >= (uint32_t)d)
+        incl += v;
+    }
+    if (lane == 63)
+      tot[par][wave] = incl;
+    wg_sync(); // also: every wave has flushed (and cleared) the previous chunk's words
+    uint32_t wave_start = 0, chunk_tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBandWaves; w++)
+    {
+      const uint32_t t = tot[par][w];
+      wave_start += w < wave ? t : 0;
+      chunk_tot += t;
+    }
+    const uint32_t excl = wave_start + incl - packed;
+    *buffered_before = excl >> 20;
+    *buffered_total = chunk_tot >> 20;
+    const uint32_t end_bits = base_bits + (chunk_tot & 0xFFFFFu);
+    const uint32_t w_first = base_bits >> 5, w_end = end_bits >> 5;
+    for (uint32_t win = w_first; win <= w_end; win += RING)
+    {
+      if (win != w_first)
+        wg_sync(); // the previous window's slots are cleared and the clearing ds_writes have landed (HuffRowCoder16, wg_sync.h)
+      if (live && (packed & 0xFFFFFu))
+      {
+        const uint32_t cur = base_bits + (excl & 0xFFFFFu);
+        uint32_t widx = cur >> 5;
+        uint32_t acc = 0;
+        uint32_t nacc = cur & 31;
+        auto put = [&](uint32_t tok, uint32_t len) { // len <= 27, tok < 2^len
+          const uint32_t total = nacc + len;
+          if (total < 32)
+          {
+            acc = (acc << len) | tok;
+            nacc = total;
+          }
+          else
+          {
+            const uint32_t over = total - 32;
+            if (widx - win < RING)
+              atomicOr(&ring[widx & (RING - 1)], (acc << ((32 - nacc) & 31)) | (tok >> over));
+            widx++;
+            acc = tok & ((1u << over) - 1u);
+            nacc = over;
+          }
+        };
+        emit(put);
+        if (nacc && widx - win < RING)
+          atomicOr(&ring[widx & (RING - 1)], acc << (32 - nacc));
+      }
+      wg_sync();
+      const uint32_t stop = min(w_end, win + RING);
+      for (uint32_t w = win + tid; w < stop; w += kBandThreads)
+      {
+        const uint32_t v = ring[w & (RING - 1)];
+        ff += (uint32_t)__builtin_popcount(ff_bytes(v));
+        out_w[w] = __builtin_bswap32(v);
+        ring[w & (RING - 1)] = 0;
+      }
+    }
+    base_bits = end_bits;
+    par ^= 1;
+  }
+};
+
+// the low n <= 63 bits of v, most significant first, in pieces put takes
+template <class Put>
+__device__ __forceinline__ void put_bits64(Put &put, unsigned long long v, uint32_t n)
+{
+  while (n > 16)
+  {
+    n -= 16;
+    put((uint32_t)(v >> n) & 0xFFFFu, 16);
+  }
+  put((uint32_t)v & ((1u << n) - 1u), n);
+}
+
+template <bool STATS>
+__device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &lds)
+{
+  auto &ac = lds.ac;
+  auto &rec_all = lds.rec_all;
+  auto &ne = lds.ne;
+  auto &tl = lds.tl;
+  auto &info = lds.info;
+  auto &buf = lds.buf;
+  auto &ring = lds.ring;
+  auto &tot = lds.tot;
+  auto &ff_total = lds.ff_total;
+  auto &hist = lds.hist;
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t by = a.by0 + blockIdx.x;
+  const uint32_t ss = a.ss, se = a.se, al = a.al, last_blk = a.blocks_x - 1;
+  RefineCoder coder;
+  if constexpr (STATS)
+  {
+    for (uint32_t i = tid; i < kBandWaves * 256; i += kBandThreads)
+      (&hist[0][0])[i] = 0;
+  }
+  else
+  {
+    ac[tid] = a.ac[tid];
+    if (tid == 0)
+      ff_total = 0;
+    if (tid < 2 * kBufWords)
+      (&buf[0][0])[tid] = 0;
+    for (uint32_t w = tid; w < kRing; w += kBandThreads)
+      ring[w] = 0;
+    coder.ring = ring;
+    coder.tot = tot;
+    coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)by * a.seg_stride);
+  }
+  uint16_t *rec = rec_all + tid * kRec16Row;
+  uint32_t *whist = hist[STATS ? wave : 0];
+  const size_t pitch = a.pitch;
+  const int16_t *src_row = a.coef + (size_t)by * 8 * pitch;
+  uint4 rows[8];
+  auto fetch = [&](uint32_t bx) { // k_prog_ac's
+    const int16_t *src = src_row + (size_t)min(bx, last_blk) * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+    {
+      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + (size_t)r * pitch));
+      rows[r] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+  };
+  fetch(tid);
+  // the run pending after the chunks so far and its buffered bits (in buf[cur]); uniform
+  uint32_t run_c = 0, be_c = 0, cur = 0;
+  uint32_t uncoded = 0;
+  wg_sync(); // the table and the cleared ring / buffers / histograms
+  for (uint32_t m0 = 0; m0 < a.blocks_x; m0 += kBandThreads)
+  {
+    const bool live = m0 + tid <= last_blk;
+    const bool last_chunk = m0 + kBandThreads >= a.blocks_x;
+    const uint32_t n_live = min(kBandThreads, a.blocks_x - m0);
+    // ---- the block's entries, correction bits and flags
+    int val[64];
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+    {
+      const uint32_t w[4] = {rows[r].x, rows[r].y, rows[r].z, rows[r].w};
+#pragma unroll
+      for (int u = 0; u < 8; u++)
+        val[r * 8 + u] = (u & 1) ? (int)w[u >> 1] >> 16 : (int)(int16_t)(w[u >> 1] & 0xFFFFu);
+    }
+    auto level = [&](int l) { // a[k]: the clamp first, so every scan of a coefficient sees one value
+      const int m = l < 0 ? -l : l;
+      return (uint32_t)(m > 1023 ? 1023 : m) >> al;
+    };
+    // A ZRL is written at every 16th zero; those behind the last a == 1 (EOB) are dropped afterwards, as k_prog_ac drops them, and
+    // what they held of correction bits is tail: `keep` entries and `used` bits stand in front of EOB's end.
+    uint32_t pos = 0, r = 0, br = 0, ncb = 0, keep = 0, used = 0;
+    bool se_one = false;
+    unsigned long long cb = 0; // the block's correction bits in order, the first one most significant of the ncb
+#pragma unroll
+    for (int k = 1; k < 64; k++)
+    {
+      const bool in = (uint32_t)k >= ss && (uint32_t)k <= se;
+      const int l = val[kZigZag[k]];
+      const uint32_t av = level(l);
+      const bool zero = in && av == 0, one = in && av == 1, big = in && av > 1;
+      const uint32_t r_new = zero ? r + 1 : r;
+      const bool zrl = zero && r_new == 16;
+      const bool wr = one || zrl;
+      rec[pos] = (uint16_t)((one ? (r << 4 | 1u | (l > 0 ? 0x100u : 0u)) : 0xF0u) | br << 9);
+      pos += wr ? 1u : 0u;
+      br = wr ? 0u : (big ? br + 1 : br);
+      r = wr ? 0u : r_new;
+      cb = big ? (cb << 1 | (av & 1u)) : cb;
+      ncb += big ? 1u : 0u;
+      keep = one ? pos : keep;
+      used = one ? ncb : used;
+      se_one = se_one || ((uint32_t)k == se && one);
+    }
+    const int n = live ? (int)keep : 0;
+    const bool nonempty = live && keep != 0, tail = live && !se_one;
+    const uint32_t tb = tail ? ncb - used : 0u;
+    const unsigned long long bne = __ballot(nonempty), btl = __ballot(tail);
+    if (lane == 0)
+    {
+      ne[wave] = bne;
+      tl[wave] = btl;
+    }
+    info[tid] = (nonempty ? 1u : 0u) | (tail ? 2u : 0u) | tb << 2;
+    if (!last_chunk)
+      fetch(m0 + kBandThreads + tid);
+    wg_sync(); // the ballots and the triples of every wave
+    // ---- the flush rule: every wave walks the chunk, in scalar registers
+    uint32_t iv[kBandWaves];
+#pragma unroll
+    for (uint32_t w = 0; w < kBandWaves; w++)
+      iv[w] = info[w * 64 + lane];
+    unsigned long long fl[kBandWaves];
+    uint32_t run = run_c, be = be_c;
+    int open_at = -1; // where the run that is open began; -1: before this chunk
+#pragma unroll
+    for (uint32_t w = 0; w < kBandWaves; w++)
+    {
+      unsigned long long f = 0;
+      for (uint32_t j = 0; j < 64; j++)
+      {
+        const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)iv[w], (int)j);
+        if (x & 1u)
+          run = be = 0;
+        if (x & 2u)
+        {
+          open_at = run == 0 ? (int)(w * 64 + j) : open_at;
+          run++;
+          be += x >> 2;
+          if (run == kFullRun || be > kMaxBuffered)
+          {
+            f |= 1ull << j;
+            run = be = 0;
+          }
+        }
+      }
+      fl[w] = f;
+    }
+    if (last_chunk)
+      run = be = 0; // the interval's end closes the run: nothing stays open
+    const unsigned long long ne0 = ne[0], ne1 = ne[1], ne2 = ne[2], ne3 = ne[3];
+    const unsigned long long tl0 = tl[0], tl1 = tl[1], tl2 = tl[2], tl3 = tl[3];
+    const uint32_t end_close = last_chunk ? n_live : kNone;
+    // where the run that holds block `from` as a tail block ends: in front of the next non-empty block behind `from`, behind the
+    // next flushing block, or with the interval; kNone: not in this chunk
+    auto close_of = [&](uint32_t from_ne, uint32_t from_fl) {
+      const uint32_t c_ne = next_block(ne0, ne1, ne2, ne3, from_ne);
+      const uint32_t c_fl = next_block(fl[0], fl[1], fl[2], fl[3], from_fl);
+      return min(min(c_ne, c_fl == kNone ? kNone : c_fl + 1), end_close);
+    };
+    // ---- this lane's tokens
+    // lane 0: the run carried in, if it ends here
+    bool pre = false;
+    uint32_t pre_sym = 0, pre_extra = 0, pre_n = 0;
+    if (tid == 0 && run_c != 0)
+    {
+      const uint32_t c0 = close_of(0, 0);
+      if (c0 != kNone)
+      {
+        pre = true;
+        eob_run_symbol(run_c + c0, pre_sym, pre_extra, pre_n);
+      }
+    }
+    // a run that begins at this block
+    bool starts = false;
+    if (tail)
+      starts = nonempty || (tid == 0 ? run_c == 0 : (block_bit(fl[0], fl[1], fl[2], fl[3], tid - 1) || !block_bit(tl0, tl1, tl2, tl3, tid - 1)));
+    const bool in_open = tail && run != 0 && (int)tid >= open_at;
+    bool has_run = false;
+    uint32_t sym = 0, extra = 0, n_extra = 0;
+    if (starts && !in_open)
+    {
+      has_run = true;
+      eob_run_symbol(close_of(tid + 1, tid) - tid, sym, extra, n_extra);
+    }
+    const uint32_t tail_here = in_open ? 0u : tb; // tail bits emitted in place
+    if constexpr (STATS)
+    {
+      if (pre)
+        atomicAdd(&whist[pre_sym], 1u);
+      if (has_run)
+        atomicAdd(&whist[sym], 1u);
+      auto add_ballot = [&](bool p, uint32_t s) {
+        const uint32_t c = (uint32_t)__popcll(__ballot(p));
+        if (lane == 0 && c)
+          atomicAdd(&whist[s], c);
+      };
+      for (int i = 0; __ballot(i < n) != 0; i++)
+      { // the lanes' i-th entries together
+        const bool on = i < n;
+        const uint32_t s = on ? ref_symbol(rec[i]) : 0xFFFFu;
+        add_ballot(s == 0x01u, 0x01u);
+        add_ballot(s == 0x11u, 0x11u);
+        add_ballot(s == 0x21u, 0x21u);
+        if (on && s != 0x01u && s != 0x11u && s != 0x21u)
+          atomicAdd(&whist[s], 1u);
+      }
+      wg_sync(); // every lane has read the ballots and its row: the next chunk may write them
+    }
+    else
+    {
+      // ---- the lane's bit count
+      uint32_t bits = 0;
+      if (pre)
+      {
+        bits += (ac[pre_sym] >> 16) + pre_n + be_c;
+        uncoded += (ac[pre_sym] >> 16) == 0 ? 1u : 0u;
+      }
+      for (int i = 0; i < n; i++)
+      {
+        const uint32_t e = rec[i], len = ac[ref_symbol(e)] >> 16;
+        bits += len + (ref_symbol(e) == 0xF0u ? 0u : 1u);
+        uncoded += len == 0 ? 1u : 0u;
+      }
+      bits += (live ? used : 0u) + tail_here; // the correction bits in front of EOB's end, and the tail if it is emitted in place
+      if (has_run)
+      {
+        bits += (ac[sym] >> 16) + n_extra;
+        uncoded += (ac[sym] >> 16) == 0 ? 1u : 0u;
+      }
+      const uint32_t *rd = buf[cur];              // what lane 0 emits of the run carried in
+      uint32_t *wr = buf[open_at < 0 ? cur : cur ^ 1u]; // where the open run's tail bits go: behind those carried, or into the clear buffer
+      uint32_t before, total;
+      coder.chunk_emit(bits | (in_open ? tb : 0u) << 20, live, &before, &total, [&](auto &put) {
+        if (pre)
+        {
+          const uint32_t code = ac[pre_sym];
+          put(code & 0xFFFFu, code >> 16);
+          put(pre_extra, pre_n);
+          uint32_t w = 0;
+          for (; w < (be_c >> 5); w++)
+          {
+            put(rd[w] >> 16, 16);
+            put(rd[w] & 0xFFFFu, 16);
+          }
+          if (be_c & 31u)
+            put_bits64(put, rd[w] >> (32 - (be_c & 31u)), be_c & 31u);
+        }
+        uint32_t left = ncb; // correction bits not yet emitted: the low `left` bits of cb
+        for (int i = 0; i < n; i++)
+        {
+          const uint32_t e = rec[i], code = ac[ref_symbol(e)];
+          put(code & 0xFFFFu, code >> 16);
+          if (ref_symbol(e) != 0xF0u)
+            put((e >> 8) & 1u, 1);
+          const uint32_t nc = ref_ncorr(e);
+          left -= nc;
+          put_bits64(put, (cb >> left) & ((1ull << nc) - 1ull), nc);
+        }
+        if (has_run)
+        {
+          const uint32_t code = ac[sym];
+          put(code & 0xFFFFu, code >> 16);
+          put(extra, n_extra);
+        }
+        put_bits64(put, cb & ((1ull << tail_here) - 1ull), tail_here);
+      });
+      // ---- the open run's tail bits join the buffer (no lane reads that buffer in this chunk)
+      if (in_open && tb)
+      {
+        uint32_t o = (open_at < 0 ? be_c : 0u) + before, left = tb;
+        while (left)
+        {
+          const uint32_t room = 32 - (o & 31u), take = min(room, left);
+          left -= take;
+          atomicOr(&wr[(o >> 5) & (kBufWords - 1)], ((uint32_t)(cb >> left) & (uint32_t)((1ull << take) - 1ull)) << (room - take));
+          o += take;
+        }
+      }
+      if (run == 0 || open_at >= 0)
+      { // the carried run has ended: its buffer is clear for the chunk after the next, the other one is current
+        if (tid < kBufWords)
+          buf[cur][tid] = 0;
+        cur ^= 1u;
+      }
+    }
+    run_c = run;
+    be_c = be;
+  }
+  if constexpr (STATS)
+  {
+    wg_sync();
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBandWaves; w++)
+      s += hist[w][tid];
+    if (s)
+      atomicAdd(&a.hist[tid], s);
+  }
+  else
+  {
+    if (uncoded)
+      atomicAdd(a.uncoded, uncoded);
+    if (coder.ff)
+      atomicAdd(&ff_total, coder.ff);
+    wg_sync();
+    if (tid == 0)
+    {
+      uint32_t ff_last;
+      a.seg_bytes[by] = coder.finish(&ff_last);
+      a.ff_counts[by] = ff_total + ff_last;
+    }
+  }
+}
+
+// one kernel per table form, as the DC scan has: the scan kind is a uniform branch (one set of LDS, the registers of the widest)
+// (two waves per SIMD, the occupancy of the Al = 0 branch on its own, hold for all three)
+template <bool STATS>
+__global__ __launch_bounds__(kBandThreads) __attribute__((amdgpu_waves_per_eu(2))) void k_prog_ac(BandArgs a)
+{
+  __shared__ BandLds<STATS> lds;
+  if (a.ah != 0)
+    band_refine<STATS>(a, lds);
+  else if (a.al != 0)
+    band_first<STATS, true>(a, lds);
+  else
+    band_first<STATS, false>(a, lds);
+}
+
+// --------------------------------------------------------------------------------------------------------- a DC refinement scan
+// One raw bit (dc >> al) & 1 per block in scan order (G.1.2.1), a workgroup per interval, a thread per 32 blocks: no table, no
+// statistics.  The last byte is padded with 1-bits.  The branch of k_prog_dc<H, V, false> that DcArgs' refine selects.
+template <int H, int V>
+__device__ __forceinline__ void dc_refine(const DcArgs &a)
+{
+  __shared__ uint32_t ff_total;
+  constexpr uint32_t kThreads = 64 * kWaves<H, V>;
+  const uint32_t tid = threadIdx.x, my = a.my0 + blockIdx.x;
+  constexpr uint32_t h = H, hd = H ? H : 1, v = V, luma = h * v, per_mcu = h ? luma + 2 : 1;
+  const uint32_t n_bits = a.mcus_x * per_mcu, n_bytes = (n_bits + 7) / 8, n_words = (n_bytes + 3) / 4;
+  uint32_t *out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)my * a.seg_stride);
+  if (tid == 0)
+    ff_total = 0;
+  __syncthreads();
+  uint32_t ff = 0;
+  for (uint32_t w = tid; w < n_words; w += kThreads)
+  {
+    uint32_t word = 0;
+    for (uint32_t b = 0; b < 32; b++)
+    {
+      const uint32_t i = w * 32 + b;
+      uint32_t bit = 1;
+      if (i < n_bits)
+      {
+        const uint32_t m = i / per_mcu, u = i - m * per_mcu;
+        const bool chroma = h != 0 && u >= luma;
+        const uint32_t comp = chroma ? 1 + (u - luma) : 0;
+        const uint32_t row = (h == 0 || chroma) ? my : my * v + u / hd, col = (h == 0 || chroma) ? m : m * h + u % hd;
+        const int16_t *p = comp == 0 ? a.coef[0] : comp == 1 ? a.coef[1] : a.coef[2];
+        const size_t pitch = comp == 0 ? a.pitch[0] : comp == 1 ? a.pitch[1] : a.pitch[2];
+        bit = ((uint32_t)((int)p[(size_t)row * 8 * pitch + (size_t)col * 8] >> a.al)) & 1u;
+      }
+      word = word << 1 | bit;
+    }
+    const uint32_t valid = min(4u, n_bytes - 4 * w); // the stream is MSB first: its bytes are the word's top ones
+    ff += (uint32_t)__builtin_popcount(ff_bytes(word) & (0xFFFFFFFFu << (8 * (4 - valid))));
+    out_w[w] = __builtin_bswap32(word);
+  }
+  if (ff)
+    atomicAdd(&ff_total, ff);
+  __syncthreads();
+  if (tid == 0)
+  {
+    a.seg_bytes[my] = n_bytes;
+    a.ff_counts[my] = ff_total;
+  }
+}
+
+template <int H, int V, bool STATS>
+__global__ __launch_bounds__((64 * kWaves<H, V>)) void k_prog_dc(DcArgs a)
+{
+  if constexpr (!STATS)
+  {
+    if (a.refine)
+    {
+      dc_refine<H, V>(a);
+      return;
+    }
+  }
+  opt_symbols::opt_kernel_body<DcChunks<H, V, DcArgs>, H, V, STATS>(a);
+}
+
 } // namespace jpegprog
 } // namespace mdct
 
@@ -498,6 +1051,16 @@ int check_band(int ss, int se)
 {
   if (ss < 1 || se > 63 || ss > se)
     return fail(MDCT_INVALID_PARAMETER, "band %d..%d (1 <= ss <= se <= 63)", ss, se);
+  return MDCT_SUCCESS;
+}
+
+// the successive approximation of a scan: Al 0..13; Ah 0 (a first scan) or Al + 1 (the scan refines the one bit below its predecessor's Al)
+int check_approx(int ah, int al)
+{
+  if (al < 0 || al > 13)
+    return fail(MDCT_INVALID_PARAMETER, "successive approximation Al %d (0..13)", al);
+  if (ah != 0 && ah != al + 1)
+    return fail(MDCT_INVALID_PARAMETER, "successive approximation Ah %d with Al %d (Ah is 0 for a first scan, Al + 1 for a refinement scan)", ah, al);
   return MDCT_SUCCESS;
 }
 
@@ -549,12 +1112,22 @@ const char *mdct_jpegprog_last_error(void) { return g_err; }
 
 int mdct_jpegprog_dc_stats(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, int cls, uint32_t *hist, uint32_t *unrepresentable, void *stream)
 {
+  return mdct_jpegprog_dc_stats_approx(planes, n_planes, interleaved, cls, 0, 0, hist, unrepresentable, stream);
+}
+
+int mdct_jpegprog_dc_stats_approx(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, int cls, int ah, int al, uint32_t *hist, uint32_t *unrepresentable,
+                                  void *stream)
+{
   if (!planes || !hist || !unrepresentable)
     return fail(MDCT_INVALID_PARAMETER, "null planes / hist / unrepresentable");
   if (cls != 0 && cls != 1)
     return fail(MDCT_INVALID_PARAMETER, "class %d (0 luminance, 1 chrominance)", cls);
   int rc, h, v;
   uint32_t per_row, n_rows;
+  if ((rc = check_approx(ah, al)))
+    return rc;
+  if (ah != 0)
+    return fail(MDCT_INVALID_PARAMETER, "Ah %d: a DC refinement scan holds raw bits and has no symbols to count", ah);
   if ((rc = check_word(hist, "hist")) || (rc = check_word(unrepresentable, "unrepresentable")) || (rc = check_dc_planes(planes, n_planes, interleaved, &h, &v, &per_row, &n_rows)))
     return rc;
   DcArgs a;
@@ -562,6 +1135,7 @@ int mdct_jpegprog_dc_stats(const mdct_jpegcoef_plane *planes, int n_planes, int 
   a.hist = hist;
   a.unrepresentable = unrepresentable;
   a.cls0 = (uint32_t)cls;
+  a.al = (uint32_t)al;
   dc_planes(a, planes, n_planes, per_row);
   const hipStream_t s = (hipStream_t)stream;
   const hipError_t e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * kHist, s);
@@ -573,9 +1147,17 @@ int mdct_jpegprog_dc_stats(const mdct_jpegcoef_plane *planes, int n_planes, int 
 int mdct_jpegprog_dc_rows(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, const mdct_jpegenc_opt_spec *specs, size_t r0, size_t r1, uint8_t *out,
                           size_t seg_stride, uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream)
 {
-  if (!planes || !specs || !out || !seg_bytes || !ff_counts || !uncoded || !unrepresentable)
-    return fail(MDCT_INVALID_PARAMETER, "null planes / specs / out / seg_bytes / ff_counts / uncoded / unrepresentable");
+  return mdct_jpegprog_dc_rows_approx(planes, n_planes, interleaved, specs, 0, 0, r0, r1, out, seg_stride, seg_bytes, ff_counts, uncoded, unrepresentable, stream);
+}
+
+int mdct_jpegprog_dc_rows_approx(const mdct_jpegcoef_plane *planes, int n_planes, int interleaved, const mdct_jpegenc_opt_spec *specs, int ah, int al, size_t r0, size_t r1,
+                                 uint8_t *out, size_t seg_stride, uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream)
+{
   int rc, h, v;
+  if ((rc = check_approx(ah, al)))
+    return rc;
+  if (!planes || (!specs && ah == 0) || !out || !seg_bytes || !ff_counts || !uncoded || !unrepresentable)
+    return fail(MDCT_INVALID_PARAMETER, "null planes / specs / out / seg_bytes / ff_counts / uncoded / unrepresentable");
   uint32_t per_row, n_rows;
   if ((rc = check_dc_planes(planes, n_planes, interleaved, &h, &v, &per_row, &n_rows)))
     return rc;
@@ -588,9 +1170,11 @@ int mdct_jpegprog_dc_rows(const mdct_jpegcoef_plane *planes, int n_planes, int i
     return rc;
   DcArgs a;
   memset(&a, 0, sizeof(a));
+  a.al = (uint32_t)al;
+  a.refine = ah != 0; // raw bits, no table: nothing can be lost or lack a code
   bool complete = true;
   static const char *const names[2] = {"DC specification", "DC chrominance specification"};
-  for (int w = 0; w < (h ? 2 : 1); w++)
+  for (int w = 0; w < (h ? 2 : 1) && ah == 0; w++)
     if ((rc = spec_codes(&specs[w], false, names[w], a.dc[w], &complete)))
       return rc;
   a.complete = complete;
@@ -607,14 +1191,22 @@ int mdct_jpegprog_dc_rows(const mdct_jpegcoef_plane *planes, int n_planes, int i
 
 int mdct_jpegprog_ac_stats(const mdct_jpegcoef_plane *plane, int ss, int se, uint32_t *hist, uint32_t *unrepresentable, void *stream)
 {
+  return mdct_jpegprog_ac_stats_approx(plane, ss, se, 0, 0, hist, unrepresentable, stream);
+}
+
+int mdct_jpegprog_ac_stats_approx(const mdct_jpegcoef_plane *plane, int ss, int se, int ah, int al, uint32_t *hist, uint32_t *unrepresentable, void *stream)
+{
   if (!plane || !hist || !unrepresentable)
     return fail(MDCT_INVALID_PARAMETER, "null plane / hist / unrepresentable");
   int rc;
-  if ((rc = check_word(hist, "hist")) || (rc = check_word(unrepresentable, "unrepresentable")) || (rc = check_coef_plane(*plane, "plane", 0)) || (rc = check_band(ss, se)))
+  if ((rc = check_word(hist, "hist")) || (rc = check_word(unrepresentable, "unrepresentable")) || (rc = check_coef_plane(*plane, "plane", 0)) || (rc = check_band(ss, se)) ||
+      (rc = check_approx(ah, al)))
     return rc;
   BandArgs a;
   memset(&a, 0, sizeof(a));
   band_plane(a, *plane, ss, se);
+  a.ah = (uint32_t)ah;
+  a.al = (uint32_t)al;
   a.hist = hist;
   a.unrepresentable = unrepresentable;
   const hipStream_t s = (hipStream_t)stream;
@@ -628,10 +1220,16 @@ int mdct_jpegprog_ac_stats(const mdct_jpegcoef_plane *plane, int ss, int se, uin
 int mdct_jpegprog_ac_rows(const mdct_jpegcoef_plane *plane, int ss, int se, size_t by0, size_t by1, const mdct_jpegenc_opt_spec *ac, uint8_t *out, size_t seg_stride,
                           uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream)
 {
+  return mdct_jpegprog_ac_rows_approx(plane, ss, se, 0, 0, by0, by1, ac, out, seg_stride, seg_bytes, ff_counts, uncoded, unrepresentable, stream);
+}
+
+int mdct_jpegprog_ac_rows_approx(const mdct_jpegcoef_plane *plane, int ss, int se, int ah, int al, size_t by0, size_t by1, const mdct_jpegenc_opt_spec *ac, uint8_t *out,
+                                 size_t seg_stride, uint32_t *seg_bytes, uint32_t *ff_counts, uint32_t *uncoded, uint32_t *unrepresentable, void *stream)
+{
   if (!plane || !out || !seg_bytes || !ff_counts || !uncoded || !unrepresentable)
     return fail(MDCT_INVALID_PARAMETER, "null plane / out / seg_bytes / ff_counts / uncoded / unrepresentable");
   int rc;
-  if ((rc = check_coef_plane(*plane, "plane", 0)) || (rc = check_band(ss, se)))
+  if ((rc = check_coef_plane(*plane, "plane", 0)) || (rc = check_band(ss, se)) || (rc = check_approx(ah, al)))
     return rc;
   if (by0 >= by1 || by1 > plane->blocks_y)
     return fail(MDCT_INVALID_PARAMETER, "block rows [%zu, %zu) of %u", by0, by1, plane->blocks_y);
@@ -648,6 +1246,8 @@ int mdct_jpegprog_ac_rows(const mdct_jpegcoef_plane *plane, int ss, int se, size
     all = all && a.ac[n << 4];
   a.complete = all;
   band_plane(a, *plane, ss, se);
+  a.ah = (uint32_t)ah;
+  a.al = (uint32_t)al;
   a.out = out;
   a.seg_bytes = seg_bytes;
   a.ff_counts = ff_counts;

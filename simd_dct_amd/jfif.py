@@ -109,18 +109,22 @@ def write_jpeg(components, width, height, specs=None, sampling=None, interleaved
 
 
 def write_progressive_jpeg(qtables, width, height, sampling, scans, *, colorspace=None):
-    """A progressive file (SOF2) with spectral selection only (T.81 Annex G, Ah = Al = 0) around the scans of libmdct_jpegprog.so.
+    """A progressive file (SOF2; T.81 Annex G: spectral selection, and successive approximation where a scan names it) around the scans
+       of libmdct_jpegprog.so.
        qtables: one table per component (64 integers 1..255, natural order); equal tables share an id, in order of appearance
        sampling: [(h, v)] per component (1 or 3)
        scans: in file order, dicts with
          'components': [(component index, td, ta)] -- one component, or all three for an interleaved DC scan
          'ss', 'se': the band; 0, 0 is the DC scan, an AC band (1 <= ss <= se <= 63) takes one component (G.1.1.1.1)
+         'ah', 'al': the scan's successive approximation (optional, 0 each; 0..13)
          'restart_interval': the scan's DRI, in MCUs (blocks of the component's own grid for one component)
-         'tables': {(table class, id): (bits16, vals)} defined in a DHT in front of the scan (a later scan may redefine an id)
+         'tables': {(table class, id): (bits16, vals)} defined in a DHT in front of the scan (a later scan may redefine an id); empty
+                   for a DC refinement scan, which uses none: no DHT is written
          'scan': bytes / uint8 array, the stuffed, RST-delimited scan as mdct_jpeg_pack_rows leaves it
        colorspace: as write_jpeg.
        Written are SOI, APP0 (or the Adobe APP14), DQT per table, SOF2, and per scan DHT, DRI, SOS and the data; then EOI.
-       read_progressive_jpeg reads such a file back (read_jpeg refuses it, as it refuses every SOF2 file).  Returns the file as bytes."""
+       read_progressive_jpeg reads such a file back where every Ah and Al is 0, jfif_sof2.read_sof2_jpeg every one (read_jpeg refuses
+       it, as it refuses every SOF2 file).  Returns the file as bytes."""
     zz = api.zigzag_table()
     nc = len(sampling)
     if nc not in (1, 3) or len(qtables) != nc:
@@ -156,9 +160,13 @@ def write_progressive_jpeg(qtables, width, height, sampling, scans, *, colorspac
             raise ValueError(f"scan {k}: components {comps} (index, DC table 0 / 1, AC table 0 / 1)")
         if not 1 <= int(sc["restart_interval"]) <= 65535:
             raise ValueError(f"scan {k}: restart interval {sc['restart_interval']} (1..65535)")
-        f.append(_seg(0xC4, b"".join(_dht(tc, th, *spec) for (tc, th), spec in sorted(sc["tables"].items()))))
+        ah, al = int(sc.get("ah", 0)), int(sc.get("al", 0))
+        if not (0 <= ah <= 13 and 0 <= al <= 13):
+            raise ValueError(f"scan {k}: successive approximation Ah {ah}, Al {al} (0..13)")
+        if sc["tables"]:
+            f.append(_seg(0xC4, b"".join(_dht(tc, th, *spec) for (tc, th), spec in sorted(sc["tables"].items()))))
         f.append(_seg(0xDD, struct.pack(">H", int(sc["restart_interval"]))))
-        f.append(_seg(0xDA, bytes([len(comps)]) + b"".join(bytes([ci + 1, (td << 4) | ta]) for ci, td, ta in comps) + bytes([ss, se, 0])))
+        f.append(_seg(0xDA, bytes([len(comps)]) + b"".join(bytes([ci + 1, (td << 4) | ta]) for ci, td, ta in comps) + bytes([ss, se, (ah << 4) | al])))
         f.append(bytes(memoryview(np.ascontiguousarray(sc["scan"]))))
     f.append(b"\xff\xd9")
     return b"".join(f)

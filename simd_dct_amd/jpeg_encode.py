@@ -338,7 +338,7 @@ def _run_scan(plane, pw, ph, lut, chroma, sc, two_launch, stream, specs=None, un
                              stream=stream)
 
 
-def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True, interleaved=False, optimize=False, progressive=False):
+def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=None, stream=None, *, two_launch=True, interleaved=False, optimize=False, progressive=False, script=None):
     """Encode an 8-bit image as a baseline JPEG (JFIF) on the GPU and return the file as bytes.
 
     image: uint8 [H, W, 3] (layout="HWC"), [3, H, W] (layout="CHW") or [H, W] (grey, any layout); a numpy array or CPU tensor is
@@ -369,6 +369,9 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     with the level shift and the quality tables makes the quantised coefficients the pixel coders are defined on, and the band coders
     saturate AC levels to +-1023 as the pixel coders do.  The tables are always made for the image: optimize=False is accepted and
     plays no part, nor does two_launch; interleaved selects the form of the DC scan.  decode_jpeg reads the file back.
+    script (with progressive=True only: ValueError otherwise): None is the file above; 'standard' is libjpeg's standard script with
+    successive approximation, what Pillow's progressive=True writes; a list of (components, ss, se, ah, al)
+    is checked by jpeg_progressive.check_script.  With a script its scans' component lists decide which DC scans are interleaved.
 
     stream: None (torch's current stream), a torch.cuda.Stream or a raw hipStream_t.  All device work of the call -- its kernels, its own
     allocations, fills and the upload of a host image, and the copies of the histogram, the scans' lengths and their bytes that the host
@@ -384,6 +387,8 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
         raise ValueError(f"optimize {optimize!r}: a bool")
     if not isinstance(progressive, (bool, np.bool_)):
         raise ValueError(f"progressive {progressive!r}: a bool")
+    if script is not None and not progressive:
+        raise ValueError("script: only with progressive=True")
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
             raise ValueError(f"image dtype {image.dtype}: uint8")
@@ -393,6 +398,10 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     sampling = sampling_of(subsampling, grey)
     sizes = component_sizes(W, H, sampling)
     luma, chroma = quality_tables(q)
+    if progressive:
+        from . import jpeg_progressive
+
+        script = jpeg_progressive.resolve_script(script, None, len(sampling), bool(interleaved) and not grey, sampling)
     dev = api._device(device)
     if isinstance(image, np.ndarray):
         image = torch.from_numpy(np.ascontiguousarray(image))
@@ -402,15 +411,12 @@ def encode_jpeg(image, quality=75, subsampling="4:2:0", layout="HWC", device=Non
     dev = image.device
     with torch.cuda.device(dev), api._on_stream(stream, dev):
         if progressive:
-            from . import jpeg_progressive
-
             mcus_x, mcus_y, padded = mcu_grid(W, H, sampling)
             planes = to_planes(image, subsampling, layout, planes=[torch.empty((ph, pw), dtype=torch.uint8, device=dev) for pw, ph in padded], stream=stream)
             tabs = [luma] + [chroma] * (len(planes) - 1)
             coefs = [torch.empty(p.shape, dtype=torch.int16, device=dev) for p in planes]
             api.u8_i16_batch("fwd", [(p, c, pw, ph, np.asarray(t, dtype=np.float32)) for p, c, (pw, ph), t in zip(planes, coefs, padded, tabs)], level_shift=True, stream=stream)
-            return jpeg_progressive.encode(torch, coefs, tabs, W, H, sampling, mcus_x, mcus_y, None, bool(interleaved) and not grey, jpeg_progressive.check_bands(None, len(planes)),
-                                           stream, saturate=True)
+            return jpeg_progressive.encode(torch, coefs, tabs, W, H, sampling, mcus_x, mcus_y, None, script, stream, saturate=True)
         if interleaved and not grey:
             scan, specs = _encode_interleaved(torch, image, W, H, sampling, subsampling, layout, (luma, chroma), stream, optimize)
             return jfif.write_jpeg([dict(qtable=luma), dict(qtable=chroma), dict(qtable=chroma)], W, H, specs=specs, sampling=sampling, interleaved=scan)

@@ -131,7 +131,7 @@ def _pack(torch, seg, counts, stride, rows, pixels, dev, stream):
     return out, off
 
 
-def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=None, optimize=True, interleaved=False, progressive=False, bands=None, stream=None):
+def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=None, optimize=True, interleaved=False, progressive=False, bands=None, script=None, stream=None):
     """Quantised coefficient planes -> a baseline JPEG file (bytes), or with progressive=True a progressive one, without a DCT.
 
     coefs: 1 or 3 int16 device tensors [rows, columns], each padded to the MCU grid of the frame (jpeg_encode.mcu_grid), in the layout
@@ -154,7 +154,13 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
     component a list of (ss, se) that tiles 1..63 in order (default: luma (1, 2), (3, 9), (10, 63), chroma (1, 63); grey as luma; anything
     else is a ValueError); without progressive it must be None.  All statistics launches run first and one copy brings every histogram
     and the loss count back; then all coding and packing launches, and one copy of the lengths.  jpeg_decode reads these files back
-    (jfif.read_progressive_jpeg, libmdct_jpegdec_prog.so)."""
+    (jfif.read_progressive_jpeg, libmdct_jpegdec_prog.so).
+    script (with progressive=True, instead of bands): None is the output above, byte for byte.  'standard' is libjpeg's standard script
+    with successive approximation (jpeg_progressive.standard_script: what Pillow's progressive=True and jpegtran -progressive write;
+    DESIGN.md section 4.12.1); a list of (components, ss, se, ah, al) is any script jpeg_progressive.check_script accepts (ValueError
+    naming the scan otherwise).  The scans' component lists decide which DC scans are interleaved (`interleaved` is not consulted); a
+    scan of all three components takes the samplings above.  Every scan keeps a restart interval per row of its own grid, a DC
+    refinement scan has no table and no statistics launch.  script without progressive=True, or together with bands: ValueError."""
     import torch
 
     _bools(optimize, interleaved)
@@ -164,6 +170,8 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
         raise ValueError("progressive=True needs optimize=True: the Annex K tables have no codes for end-of-band runs")
     if bands is not None and not progressive:
         raise ValueError("bands: only with progressive=True")
+    if script is not None and not progressive:
+        raise ValueError("script: only with progressive=True")
     sampling = [(int(h), int(v)) for h, v in sampling]
     nc = len(sampling)
     if nc not in (1, 3) or len(coefs) != nc or len(qtables) != nc:
@@ -177,7 +185,7 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
     if progressive:
         from . import jpeg_progressive
 
-        bands = jpeg_progressive.check_bands(bands, nc)
+        script = jpeg_progressive.resolve_script(script, bands, nc, bool(interleaved), sampling)
     tabs = []
     for k, q in enumerate(qtables):
         q = np.asarray(q).reshape(-1)
@@ -195,7 +203,7 @@ def encode_coefficients(coefs, qtables, width, height, sampling, *, colorspace=N
     if progressive:
         from . import jpeg_progressive
 
-        return jpeg_progressive.encode(torch, coefs, tabs, width, height, sampling, mcus_x, mcus_y, colorspace, bool(interleaved), bands, stream)
+        return jpeg_progressive.encode(torch, coefs, tabs, width, height, sampling, mcus_x, mcus_y, colorspace, script, stream)
     grey = nc == 1
     dev = coefs[0].device
     with torch.cuda.device(dev), api._on_stream(stream, dev):
@@ -274,7 +282,7 @@ def plan_transform(width, height, sampling, transform, trim):
     return (size["x"], size["y"]), (size["x"], size["y"]), [(h, v) for h, v in sampling]
 
 
-def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleaved=False, progressive=False, device=None, stream=None):
+def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleaved=False, progressive=False, script=None, device=None, stream=None):
     """Rewrite a baseline JPEG, or a progressive one decode_jpeg reads, without touching its coefficients (jpegtran):
     decode_coefficients, the optional transform, encode_coefficients.  Returns the new file as bytes.
 
@@ -287,7 +295,8 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     MCU row (three components with 4:4:4, 4:2:2 or 4:2:0 AFTER the transform: ValueError otherwise, before any device work).  Either way
     the output goes through the per-interval decoder ever after, whatever the input's scan form and restart interval were.
     progressive=True: the output is a progressive file with spectral selection (encode_coefficients: optimize must be True; interleaved
-    selects the form of its DC scan).
+    selects the form of its DC scan).  script (with progressive=True only: ValueError otherwise): None, 'standard' -- libjpeg's standard
+    script with successive approximation, the file jpegtran -progressive writes -- or a list, as encode_coefficients takes it.
     The quantisation tables (one per component, equal ones shared) and the colour space (grey, YCbCr, Adobe RGB) survive.
     Blocks of the padded planes beyond a component's own grid are zero after a non-interleaved input; an interleaved output codes them
     as they are -- they are invisible, which is not a loss.
@@ -302,7 +311,7 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
     neighbours that were not).
 
     Out of scope: copying EXIF, ICC or comment segments (APPn and COM are dropped but for the colour-space markers); arithmetic-coded
-    INPUT; successive approximation, in or out; jpegtran's default of leaving an unmirrored edge strip in place (here: perfect,
+    INPUT; jpegtran's default of leaving an unmirrored edge strip in place (here: perfect,
     trim, or an error); re-quantising (changing quality)."""
     import torch
 
@@ -311,6 +320,8 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
         raise ValueError(f"progressive {progressive!r}: a bool")
     if progressive and not optimize:
         raise ValueError("progressive=True needs optimize=True: the Annex K tables have no codes for end-of-band runs")
+    if script is not None and not progressive:
+        raise ValueError("script: only with progressive=True")
     if transform is not None and transform not in MIRRORED:
         raise ValueError(f"transform {transform!r} (None or one of {', '.join(TRANSFORMS)})")
     info = jpeg_decode.read_file(data)
@@ -337,4 +348,4 @@ def transcode_jpeg(data, *, transform=None, trim=False, optimize=True, interleav
         if transform in TRANSPOSING:
             qtables = [t.T for t in qtables]
     return encode_coefficients(coefs, [np.rint(t).astype(np.int64).reshape(64) for t in qtables], ow, oh, osampling, colorspace=info["colorspace"],
-                               optimize=bool(optimize), interleaved=bool(interleaved), progressive=bool(progressive), stream=stream)
+                               optimize=bool(optimize), interleaved=bool(interleaved), progressive=bool(progressive), script=script, stream=stream)
