@@ -22,7 +22,8 @@
 //            another.  A non-empty block codes EOBn of (pending mod 32767) in front of its entries; the tail block whose ordinal
 //            reaches 32767 codes the full run (0xE0 and 14 one-bits) itself.
 //   symbols  the token's bits join the lane's bit count; the scan of the counts, the ring, the 0xFF count and finish are
-//            HuffSeqCoder16's (BandCoder below).  After the last chunk one lane writes the run still pending.
+//            RingWriter's (huffman_rows.h; BandCoder below).  After the last chunk one lane writes the run still pending.
+// What the scan kinds share around their middles -- set-up, fetch, unpacking, the histogram of entries, the epilogues -- is BandRow.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -157,14 +158,14 @@ __device__ __forceinline__ uint32_t run_after(int I, uint32_t carry, const unsig
   return (uint32_t)(I - (w * 64 + j)) + (uint32_t)((tl[w] >> j) & 1ull);
 }
 
-// HuffSeqCoder16 for a band: no DC token; an optional run token (code of `sym`, then n_extra bits) in front of the lane's entries, no
-// EOB behind them.  State, scan, ring, 0xFF count and finish are the base's.
-struct BandCoder : HuffSeqCoder16<(int)kBandWaves, kRing>
+using BandWriter = RingWriter<(int)kBandWaves, kRing>;
+
+// The coder of a first scan's chunk: no DC token; an optional run token (code of `sym`, then n_extra bits) in front of the lane's
+// entries, no EOB behind them.
+struct BandCoder : BandWriter
 {
   __device__ __forceinline__ void chunk_band(const uint16_t *rec, int n, bool live, bool has_run, uint32_t sym, uint32_t extra, uint32_t n_extra, const uint32_t *ac)
   {
-    constexpr uint32_t RING = kRing;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t *rec2 = reinterpret_cast<const uint32_t *>(rec);
     const uint32_t run_code = ac[sym & 0xFFu];
     uint32_t bits = 0;
@@ -172,93 +173,16 @@ struct BandCoder : HuffSeqCoder16<(int)kBandWaves, kRing>
     {
       if (has_run)
         bits = (run_code >> 16) + n_extra;
-      for (int i = 0; i < n; i += 2)
+      bits += huff_count16(rec2, n, ac);
+    }
+    write(bits, live, [&](auto &put) {
+      if (has_run)
       {
-        const uint32_t w = rec2[i >> 1];
-        bits += huff_ac_token12(w & 0xFFFFu, ac).len;
-        if (i + 1 < n)
-          bits += huff_ac_token12(w >> 16, ac).len;
+        put(run_code & 0xFFFFu, run_code >> 16);
+        put(extra, n_extra);
       }
-    }
-    uint32_t incl = bits;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-      const uint32_t v = __shfl_up(incl, d, 64);
-      if (lane >= (uint32_t)d)
-        incl += v;
-    }
-    if (lane == 63)
-      tot[par][wave] = incl;
-    wg_sync(); // also: every wave has flushed (and cleared) the previous chunk's words
-    uint32_t wave_start = 0, chunk_bits = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kBandWaves; w++)
-    {
-      const uint32_t t = tot[par][w];
-      wave_start += w < wave ? t : 0;
-      chunk_bits += t;
-    }
-    const uint32_t end_bits = base_bits + chunk_bits;
-    const uint32_t w_first = base_bits >> 5, w_end = end_bits >> 5;
-    for (uint32_t win = w_first; win <= w_end; win += RING)
-    {
-      if (win != w_first)
-        wg_sync(); // the previous window's slots are cleared and the clearing ds_writes have landed (HuffRowCoder16, wg_sync.h)
-      if (live)
-      {
-        const uint32_t cur = base_bits + wave_start + (incl - bits);
-        uint32_t widx = cur >> 5;
-        uint32_t acc = 0;
-        uint32_t nacc = cur & 31;
-        auto put = [&](uint32_t tok, uint32_t len) { // len <= 27, tok < 2^len
-          const uint32_t total = nacc + len;
-          if (total < 32)
-          {
-            acc = (acc << len) | tok;
-            nacc = total;
-          }
-          else
-          {
-            const uint32_t over = total - 32;
-            if (widx - win < RING)
-              atomicOr(&ring[widx & (RING - 1)], (acc << ((32 - nacc) & 31)) | (tok >> over));
-            widx++;
-            acc = tok & ((1u << over) - 1u);
-            nacc = over;
-          }
-        };
-        if (has_run)
-        {
-          put(run_code & 0xFFFFu, run_code >> 16);
-          put(extra, n_extra);
-        }
-        for (int i = 0; i < n; i += 2)
-        {
-          const uint32_t w = rec2[i >> 1];
-          const HuffTok ta = huff_ac_token12(w & 0xFFFFu, ac);
-          put(ta.bits, ta.len);
-          if (i + 1 < n)
-          {
-            const HuffTok tb = huff_ac_token12(w >> 16, ac);
-            put(tb.bits, tb.len);
-          }
-        }
-        if (nacc && widx - win < RING)
-          atomicOr(&ring[widx & (RING - 1)], acc << (32 - nacc));
-      }
-      wg_sync();
-      const uint32_t stop = min(w_end, win + RING);
-      for (uint32_t w = win + tid; w < stop; w += kBandThreads)
-      {
-        const uint32_t v = ring[w & (RING - 1)];
-        ff += (uint32_t)__builtin_popcount(ff_bytes(v));
-        out_w[w] = __builtin_bswap32(v);
-        ring[w & (RING - 1)] = 0;
-      }
-    }
-    base_bits = end_bits;
-    par ^= 1;
+      huff_put16(put, rec2, n, ac);
+    });
   }
 
   // one thread, after the last chunk (behind a workgroup barrier) and before finish: the run still pending, at most 16 + 14 bits.  The
@@ -301,47 +225,55 @@ struct BandLds
   uint32_t buf[STATS ? 1 : 2][STATS ? 1 : kBufWords]; // the tail bits of the open run, MSB first; the other one is clear
 };
 
-// A first scan (Ah = 0).  SHIFT: Al > 0 -- the level is |v| >> al with v's sign (clamped first); a level that becomes 0 is a zero for
-// runs and tail flag alike
-template <bool STATS, bool SHIFT>
-__device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &lds)
+// What the scan kinds of a band share, around a coder of the scan's kind: the set-up of LDS and of the segment, the lane's block (its
+// 8 rows streamed into registers one chunk ahead, unpacked to 64 levels), the histogram of the lanes' entries and the epilogues.
+template <bool STATS, class Coder>
+struct BandRow
 {
-  auto &ac = lds.ac;
-  auto &rec_all = lds.rec_all;
-  auto &ne = lds.ne;
-  auto &tl = lds.tl;
-  auto &ring = lds.ring;
-  auto &tot = lds.tot;
-  auto &ff_total = lds.ff_total;
-  auto &hist = lds.hist;
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t by = a.by0 + blockIdx.x;
-  const uint32_t ss = a.ss, se = a.se, last_blk = a.blocks_x - 1;
-  BandCoder coder;
-  if constexpr (STATS)
-  {
-    for (uint32_t i = tid; i < kBandWaves * 256; i += kBandThreads)
-      (&hist[0][0])[i] = 0;
-  }
-  else
-  {
-    ac[tid] = a.ac[tid];
-    if (tid == 0)
-      ff_total = 0;
-    for (uint32_t w = tid; w < kRing; w += kBandThreads)
-      ring[w] = 0;
-    coder.ring = ring;
-    coder.tot = tot;
-    coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)by * a.seg_stride);
-  }
-  uint16_t *rec = rec_all + tid * kRec16Row;
-  uint32_t *whist = hist[STATS ? wave : 0];
-  const size_t pitch = a.pitch;
-  const int16_t *src_row = a.coef + (size_t)by * 8 * pitch;
+  const BandArgs &a;
+  BandLds<STATS> &lds;
+  uint32_t tid, lane, wave, by, last_blk;
+  uint16_t *rec;   // the lane's LDS row
+  uint32_t *whist; // STATS: the wave's histogram
+  const int16_t *src_row;
+  size_t pitch;
   uint4 rows[8];
+  Coder coder;
+
+  // ends with the first chunk's rows requested; the caller's barrier publishes the table and the cleared ring / histograms
+  __device__ __forceinline__ BandRow(const BandArgs &a_, BandLds<STATS> &lds_) : a(a_), lds(lds_)
+  {
+    tid = threadIdx.x;
+    lane = tid & 63;
+    wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    by = a.by0 + blockIdx.x;
+    last_blk = a.blocks_x - 1;
+    if constexpr (STATS)
+    {
+      for (uint32_t i = tid; i < kBandWaves * 256; i += kBandThreads)
+        (&lds.hist[0][0])[i] = 0;
+    }
+    else
+    {
+      lds.ac[tid] = a.ac[tid];
+      if (tid == 0)
+        lds.ff_total = 0;
+      for (uint32_t w = tid; w < kRing; w += kBandThreads)
+        lds.ring[w] = 0;
+      coder.ring = lds.ring;
+      coder.tot = lds.tot;
+      coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)by * a.seg_stride);
+    }
+    rec = lds.rec_all + tid * kRec16Row;
+    whist = lds.hist[STATS ? wave : 0];
+    pitch = a.pitch;
+    src_row = a.coef + (size_t)by * 8 * pitch;
+    fetch(tid);
+  }
+
   // the 8 rows of block min(bx, last) of the block row (lanes past the row's end redo the last block); streamed once
-  auto fetch = [&](uint32_t bx) {
+  __device__ __forceinline__ void fetch(uint32_t bx)
+  {
     const int16_t *src = src_row + (size_t)min(bx, last_blk) * 8;
 #pragma unroll
     for (int r = 0; r < 8; r++)
@@ -349,16 +281,11 @@ __device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &ld
       const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + (size_t)r * pitch));
       rows[r] = make_uint4(v.x, v.y, v.z, v.w);
     }
-  };
-  fetch(tid);
-  uint32_t carry = 0;   // the run pending after the chunks so far, mod 32767; uniform
-  uint32_t lost = 0, uncoded = 0;
-  wg_sync(); // the table and the cleared ring / histograms
-  for (uint32_t m0 = 0; m0 < a.blocks_x; m0 += kBandThreads)
+  }
+
+  // the fetched block's 64 levels in raster order
+  __device__ __forceinline__ void unpack(int (&val)[64]) const
   {
-    const bool live = m0 + tid <= last_blk;
-    // ---- levels of the band -> entries (compact_levels16 with the band's bounds; AC clamped to +-1023 and counted)
-    int val[64];
 #pragma unroll
     for (int r = 0; r < 8; r++)
     {
@@ -367,6 +294,80 @@ __device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &ld
       for (int u = 0; u < 8; u++)
         val[r * 8 + u] = (u & 1) ? (int)w[u >> 1] >> 16 : (int)(int16_t)(w[u >> 1] & 0xFFFFu);
     }
+  }
+
+  // STATS: the symbols sym(i) of the lane's n entries join the wave's histogram, the lanes' i-th entries together; s0, s1, s2 are
+  // symbols that many lanes hold at once: one add per wave (template parameters: as function arguments they cost the refinement
+  // scan's statistics 4 %)
+  template <uint32_t s0, uint32_t s1, uint32_t s2, class Sym>
+  __device__ __forceinline__ void count_entries(int n, Sym sym)
+  {
+    auto add_ballot = [&](bool p, uint32_t s) {
+      const uint32_t c = (uint32_t)__popcll(__ballot(p));
+      if (lane == 0 && c)
+        atomicAdd(&whist[s], c);
+    };
+    for (int i = 0; __ballot(i < n) != 0; i++)
+    {
+      const bool on = i < n;
+      const uint32_t s = on ? sym(i) : 0xFFFFu;
+      add_ballot(s == s0, s0);
+      add_ballot(s == s1, s1);
+      add_ballot(s == s2, s2);
+      if (on && s != s0 && s != s1 && s != s2)
+        atomicAdd(&whist[s], 1u);
+    }
+  }
+
+  // STATS, after the last chunk: the waves' histograms join the caller's
+  __device__ __forceinline__ void sum_hist()
+  {
+    wg_sync();
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kBandWaves; w++)
+      s += lds.hist[w][tid];
+    if (s)
+      atomicAdd(&a.hist[tid], s);
+  }
+
+  // the coder, after the last chunk: the segment's padded end, its length and its 0xFF count
+  __device__ __forceinline__ void finish()
+  {
+    if (coder.ff)
+      atomicAdd(&lds.ff_total, coder.ff);
+    wg_sync();
+    if (tid == 0)
+    {
+      uint32_t ff_last;
+      a.seg_bytes[by] = coder.finish(&ff_last);
+      a.ff_counts[by] = lds.ff_total + ff_last;
+    }
+  }
+};
+
+// A first scan (Ah = 0).  SHIFT: Al > 0 -- the level is |v| >> al with v's sign (clamped first); a level that becomes 0 is a zero for
+// runs and tail flag alike
+template <bool STATS, bool SHIFT>
+__device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &lds)
+{
+  BandRow<STATS, BandCoder> row(a, lds);
+  auto &ac = lds.ac;
+  auto &ne = lds.ne;
+  auto &tl = lds.tl;
+  const uint32_t tid = row.tid, lane = row.lane, wave = row.wave;
+  const uint32_t ss = a.ss, se = a.se, last_blk = row.last_blk;
+  uint16_t *rec = row.rec;
+  uint32_t *whist = row.whist;
+  uint32_t carry = 0; // the run pending after the chunks so far, mod 32767; uniform
+  uint32_t lost = 0, uncoded = 0;
+  wg_sync(); // the table and the cleared ring / histograms
+  for (uint32_t m0 = 0; m0 < a.blocks_x; m0 += kBandThreads)
+  {
+    const bool live = m0 + tid <= last_blk;
+    // ---- levels of the band -> entries (compact_levels16 with the band's bounds; AC clamped to +-1023 and counted)
+    int val[64];
+    row.unpack(val);
     uint32_t pos = 0, r12 = 0, clamped = 0;
     bool se_coded = false;
 #pragma unroll
@@ -402,7 +403,7 @@ __device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &ld
       tl[wave] = btl;
     }
     if (m0 + kBandThreads < a.blocks_x)
-      fetch(m0 + kBandThreads + tid);
+      row.fetch(m0 + kBandThreads + tid);
     wg_sync(); // the ballots of every wave
     // ---- the end-of-band run in front of this block
     const uint32_t r = run_after(nonempty ? (int)tid - 1 : (int)tid, carry, ne, tl);
@@ -426,22 +427,7 @@ __device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &ld
     {
       if (has_run)
         atomicAdd(&whist[sym], 1u);
-      // a symbol that many lanes hold at once: one add per wave
-      auto add_ballot = [&](bool p, uint32_t s) {
-        const uint32_t c = (uint32_t)__popcll(__ballot(p));
-        if (lane == 0 && c)
-          atomicAdd(&whist[s], c);
-      };
-      for (int i = 0; __ballot(i < n) != 0; i++)
-      { // the lanes' i-th entries together
-        const bool on = i < n;
-        const uint32_t s = on ? opt_symbols::ac_symbol12(rec[i]) : 0xFFFFu;
-        add_ballot(s == 0x01u, 0x01u);
-        add_ballot(s == 0x02u, 0x02u);
-        add_ballot(s == 0x11u, 0x11u);
-        if (on && s != 0x01u && s != 0x02u && s != 0x11u)
-          atomicAdd(&whist[s], 1u);
-      }
+      row.template count_entries<0x01u, 0x02u, 0x11u>(n, [&](int i) { return opt_symbols::ac_symbol12(rec[i]); });
       wg_sync(); // every lane has read the ballots: the next chunk may write them (the coder's barriers)
     }
     else
@@ -453,7 +439,7 @@ __device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &ld
         for (int i = 0; i < n; i++)
           uncoded += (ac[opt_symbols::ac_symbol12(rec[i])] >> 16) == 0 ? 1u : 0u;
       }
-      coder.chunk_band(rec, n, live, has_run, sym, extra, n_extra, ac);
+      row.coder.chunk_band(rec, n, live, has_run, sym, extra, n_extra, ac);
     }
   }
   // ---- the run still pending ends with the interval
@@ -466,13 +452,7 @@ __device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &ld
   {
     if (tid == 0 && carry)
       atomicAdd(&whist[sym], 1u);
-    wg_sync();
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kBandWaves; w++)
-      s += hist[w][tid];
-    if (s)
-      atomicAdd(&a.hist[tid], s);
+    row.sum_hist();
   }
   else
   {
@@ -482,16 +462,8 @@ __device__ __forceinline__ void band_first(const BandArgs &a, BandLds<STATS> &ld
       atomicAdd(a.uncoded, uncoded);
     wg_sync(); // every wave has flushed and cleared the last chunk's words
     if (tid == 0 && carry)
-      coder.flush_run(ac[sym], extra, n_extra); // a word it completes joins this thread's 0xFF count, added below
-    if (coder.ff)
-      atomicAdd(&ff_total, coder.ff);
-    wg_sync();
-    if (tid == 0)
-    {
-      uint32_t ff_last;
-      a.seg_bytes[by] = coder.finish(&ff_last);
-      a.ff_counts[by] = ff_total + ff_last;
-    }
+      row.coder.flush_run(ac[sym], extra, n_extra); // a word it completes joins this thread's 0xFF count, added by finish
+    row.finish();
   }
 }
 
@@ -542,85 +514,9 @@ __device__ __forceinline__ bool block_bit(unsigned long long m0, unsigned long l
 __device__ __forceinline__ uint32_t ref_symbol(uint32_t e) { return e & 0xFFu; }
 __device__ __forceinline__ uint32_t ref_ncorr(uint32_t e) { return e >> 9; }
 
-// BandCoder's window loop for a lane whose bits are a sequence only it can replay: emit(put) calls put(bits, len <= 16) in stream
-// order, the same calls every time.  packed = the lane's bit count | the bits it leaves in the carried buffer << 20 (both scanned at
-// once: a chunk holds < 2^19 bits and an open run <= 1000 buffered ones); *buffered_before: the second scan's exclusive prefix.
-struct RefineCoder : BandCoder
-{
-  template <class Emit>
-  __device__ __forceinline__ void chunk_emit(uint32_t packed, bool live, uint32_t *buffered_before, uint32_t *buffered_total, Emit emit)
-  {
-    constexpr uint32_t RING = kRing;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint32_t incl = packed;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-      const uint32_t v = __shfl_up(incl, d, 64);
-      if (lane >= (uint32_t)d)
-        incl += v;
-    }
-    if (lane == 63)
-      tot[par][wave] = incl;
-    wg_sync(); // also: every wave has flushed (and cleared) the previous chunk's words
-    uint32_t wave_start = 0, chunk_tot = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kBandWaves; w++)
-    {
-      const uint32_t t = tot[par][w];
-      wave_start += w < wave ? t : 0;
-      chunk_tot += t;
-    }
-    const uint32_t excl = wave_start + incl - packed;
-    *buffered_before = excl >> 20;
-    *buffered_total = chunk_tot >> 20;
-    const uint32_t end_bits = base_bits + (chunk_tot & 0xFFFFFu);
-    const uint32_t w_first = base_bits >> 5, w_end = end_bits >> 5;
-    for (uint32_t win = w_first; win <= w_end; win += RING)
-    {
-      if (win != w_first)
-        wg_sync(); // the previous window's slots are cleared and the clearing ds_writes have landed (HuffRowCoder16, wg_sync.h)
-      if (live && (packed & 0xFFFFFu))
-      {
-        const uint32_t cur = base_bits + (excl & 0xFFFFFu);
-        uint32_t widx = cur >> 5;
-        uint32_t acc = 0;
-        uint32_t nacc = cur & 31;
-        auto put = [&](uint32_t tok, uint32_t len) { // len <= 27, tok < 2^len
-          const uint32_t total = nacc + len;
-          if (total < 32)
-          {
-            acc = (acc << len) | tok;
-            nacc = total;
-          }
-          else
-          {
-            const uint32_t over = total - 32;
-            if (widx - win < RING)
-              atomicOr(&ring[widx & (RING - 1)], (acc << ((32 - nacc) & 31)) | (tok >> over));
-            widx++;
-            acc = tok & ((1u << over) - 1u);
-            nacc = over;
-          }
-        };
-        emit(put);
-        if (nacc && widx - win < RING)
-          atomicOr(&ring[widx & (RING - 1)], acc << (32 - nacc));
-      }
-      wg_sync();
-      const uint32_t stop = min(w_end, win + RING);
-      for (uint32_t w = win + tid; w < stop; w += kBandThreads)
-      {
-        const uint32_t v = ring[w & (RING - 1)];
-        ff += (uint32_t)__builtin_popcount(ff_bytes(v));
-        out_w[w] = __builtin_bswap32(v);
-        ring[w & (RING - 1)] = 0;
-      }
-    }
-    base_bits = end_bits;
-    par ^= 1;
-  }
-};
+// A refinement lane's bits are a sequence only it can replay, and the writer scans two counts at once: the lane's bit count, and
+// above kBitsMask the bits it leaves in the carried buffer (a chunk holds < 2^19 bits and an open run <= 1000 buffered ones).
+constexpr uint32_t kBitsMask = 0xFFFFFu, kBufferedShift = 20;
 
 // the low n <= 63 bits of v, most significant first, in pieces put takes
 template <class Put>
@@ -637,54 +533,22 @@ __device__ __forceinline__ void put_bits64(Put &put, unsigned long long v, uint3
 template <bool STATS>
 __device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &lds)
 {
+  BandRow<STATS, BandWriter> row(a, lds);
+  auto &coder = row.coder;
   auto &ac = lds.ac;
-  auto &rec_all = lds.rec_all;
   auto &ne = lds.ne;
   auto &tl = lds.tl;
   auto &info = lds.info;
   auto &buf = lds.buf;
-  auto &ring = lds.ring;
-  auto &tot = lds.tot;
-  auto &ff_total = lds.ff_total;
-  auto &hist = lds.hist;
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t by = a.by0 + blockIdx.x;
-  const uint32_t ss = a.ss, se = a.se, al = a.al, last_blk = a.blocks_x - 1;
-  RefineCoder coder;
-  if constexpr (STATS)
+  const uint32_t tid = row.tid, lane = row.lane, wave = row.wave;
+  const uint32_t ss = a.ss, se = a.se, al = a.al, last_blk = row.last_blk;
+  uint16_t *rec = row.rec;
+  uint32_t *whist = row.whist;
+  if constexpr (!STATS)
   {
-    for (uint32_t i = tid; i < kBandWaves * 256; i += kBandThreads)
-      (&hist[0][0])[i] = 0;
-  }
-  else
-  {
-    ac[tid] = a.ac[tid];
-    if (tid == 0)
-      ff_total = 0;
     if (tid < 2 * kBufWords)
       (&buf[0][0])[tid] = 0;
-    for (uint32_t w = tid; w < kRing; w += kBandThreads)
-      ring[w] = 0;
-    coder.ring = ring;
-    coder.tot = tot;
-    coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)by * a.seg_stride);
   }
-  uint16_t *rec = rec_all + tid * kRec16Row;
-  uint32_t *whist = hist[STATS ? wave : 0];
-  const size_t pitch = a.pitch;
-  const int16_t *src_row = a.coef + (size_t)by * 8 * pitch;
-  uint4 rows[8];
-  auto fetch = [&](uint32_t bx) { // k_prog_ac's
-    const int16_t *src = src_row + (size_t)min(bx, last_blk) * 8;
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-    {
-      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(src + (size_t)r * pitch));
-      rows[r] = make_uint4(v.x, v.y, v.z, v.w);
-    }
-  };
-  fetch(tid);
   // the run pending after the chunks so far and its buffered bits (in buf[cur]); uniform
   uint32_t run_c = 0, be_c = 0, cur = 0;
   uint32_t uncoded = 0;
@@ -696,14 +560,7 @@ __device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &l
     const uint32_t n_live = min(kBandThreads, a.blocks_x - m0);
     // ---- the block's entries, correction bits and flags
     int val[64];
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-    {
-      const uint32_t w[4] = {rows[r].x, rows[r].y, rows[r].z, rows[r].w};
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-        val[r * 8 + u] = (u & 1) ? (int)w[u >> 1] >> 16 : (int)(int16_t)(w[u >> 1] & 0xFFFFu);
-    }
+    row.unpack(val);
     auto level = [&](int l) { // a[k]: the clamp first, so every scan of a coefficient sees one value
       const int m = l < 0 ? -l : l;
       return (uint32_t)(m > 1023 ? 1023 : m) >> al;
@@ -744,7 +601,7 @@ __device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &l
     }
     info[tid] = (nonempty ? 1u : 0u) | (tail ? 2u : 0u) | tb << 2;
     if (!last_chunk)
-      fetch(m0 + kBandThreads + tid);
+      row.fetch(m0 + kBandThreads + tid);
     wg_sync(); // the ballots and the triples of every wave
     // ---- the flush rule: every wave walks the chunk, in scalar registers
     uint32_t iv[kBandWaves];
@@ -821,21 +678,7 @@ __device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &l
         atomicAdd(&whist[pre_sym], 1u);
       if (has_run)
         atomicAdd(&whist[sym], 1u);
-      auto add_ballot = [&](bool p, uint32_t s) {
-        const uint32_t c = (uint32_t)__popcll(__ballot(p));
-        if (lane == 0 && c)
-          atomicAdd(&whist[s], c);
-      };
-      for (int i = 0; __ballot(i < n) != 0; i++)
-      { // the lanes' i-th entries together
-        const bool on = i < n;
-        const uint32_t s = on ? ref_symbol(rec[i]) : 0xFFFFu;
-        add_ballot(s == 0x01u, 0x01u);
-        add_ballot(s == 0x11u, 0x11u);
-        add_ballot(s == 0x21u, 0x21u);
-        if (on && s != 0x01u && s != 0x11u && s != 0x21u)
-          atomicAdd(&whist[s], 1u);
-      }
+      row.template count_entries<0x01u, 0x11u, 0x21u>(n, [&](int i) { return ref_symbol(rec[i]); });
       wg_sync(); // every lane has read the ballots and its row: the next chunk may write them
     }
     else
@@ -861,8 +704,8 @@ __device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &l
       }
       const uint32_t *rd = buf[cur];              // what lane 0 emits of the run carried in
       uint32_t *wr = buf[open_at < 0 ? cur : cur ^ 1u]; // where the open run's tail bits go: behind those carried, or into the clear buffer
-      uint32_t before, total;
-      coder.chunk_emit(bits | (in_open ? tb : 0u) << 20, live, &before, &total, [&](auto &put) {
+      // a lane without bits writes nothing
+      const uint32_t before = coder.template write<kBitsMask>(bits | (in_open ? tb : 0u) << kBufferedShift, live && bits, [&](auto &put) {
         if (pre)
         {
           const uint32_t code = ac[pre_sym];
@@ -895,7 +738,7 @@ __device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &l
           put(extra, n_extra);
         }
         put_bits64(put, cb & ((1ull << tail_here) - 1ull), tail_here);
-      });
+      }).before >> kBufferedShift;
       // ---- the open run's tail bits join the buffer (no lane reads that buffer in this chunk)
       if (in_open && tb)
       {
@@ -919,28 +762,12 @@ __device__ __forceinline__ void band_refine(const BandArgs &a, BandLds<STATS> &l
     be_c = be;
   }
   if constexpr (STATS)
-  {
-    wg_sync();
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kBandWaves; w++)
-      s += hist[w][tid];
-    if (s)
-      atomicAdd(&a.hist[tid], s);
-  }
+    row.sum_hist();
   else
   {
     if (uncoded)
       atomicAdd(a.uncoded, uncoded);
-    if (coder.ff)
-      atomicAdd(&ff_total, coder.ff);
-    wg_sync();
-    if (tid == 0)
-    {
-      uint32_t ff_last;
-      a.seg_bytes[by] = coder.finish(&ff_last);
-      a.ff_counts[by] = ff_total + ff_last;
-    }
+    row.finish();
   }
 }
 

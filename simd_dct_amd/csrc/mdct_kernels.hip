@@ -1686,7 +1686,7 @@ __global__ __launch_bounds__(64) void k_u8_records(U8RecArgs a)
 // writes and later reads only its own row -- and the chunk coder of k_huffman_rows.  The 3 B/px of records that k_u8_records writes and
 // k_huffman_rows reads back (two thirds of them padding) never exist: 1 B/px in, ~0.2 B/px out.  One workgroup of WAVES
 // waves per block row (= restart interval); the next chunk's pixel rows are loaded while the current one is coded.
-// A wave's first block needs the previous wave's last DC as predictor, which is computed in the same pass: LATE_DC.
+// A wave's first block needs the previous wave's last DC as predictor, which is computed in the same pass: the coder's DC exchange.
 // Byte for byte the segments of mdct_fwd_u8_records + mdct_huffman_rows.
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t kFusedRing = 1024; // words of bit stream held in LDS (2 bit/px over a 256-block chunk; denser chunks take several windows)

@@ -248,16 +248,14 @@ __global__ __launch_bounds__(kHuffChunk) void k_huffman_rows(HuffArgs a)
   const uint8_t *g_rn = a.runs + row_blk0 * 64;
   const uint8_t *g_ct = a.counts + row_blk0;
   uint32_t *rec_lds = rec_all[wave];
-  HuffRowCoder<kHuffWaves, kHuffStage, true, false> coder;
+  HuffRowCoder<kHuffWaves, kHuffStage> coder;
   coder.ac = ac;
   coder.dc = dc;
   coder.ring = ring;
   coder.tot = tot;
-  coder.dcx = nullptr;
   coder.out_w = reinterpret_cast<uint32_t *>(a.out + (size_t)row * a.seg_stride);
   coder.zrl = a.ac[0xF0]; // size << 16 | code (kernel arguments: scalar registers)
   coder.eob = a.ac[0x00];
-  coder.bpr = a.bpr;
 
   // the head of the wave's 64 records: kHuffPieces pieces per block, kHuffPieces per lane
   u32x2 plv[kHuffPieces];
@@ -310,7 +308,7 @@ __global__ __launch_bounds__(kHuffChunk) void k_huffman_rows(HuffArgs a)
     if (c0 + kHuffChunk < a.bpr)
       fetch(c0w + kHuffChunk); // in flight while this chunk is coded
     wave_sync();
-    coder.chunk(c0, rec_lds + lane * kRecSkew, n, live, prev_dc, reinterpret_cast<const int16_t *>(g_lv + (live ? bx : 0u) * 128u), g_rn + (live ? bx : 0u) * 64u);
+    coder.chunk(rec_lds + lane * kRecSkew, n, live, prev_dc, reinterpret_cast<const int16_t *>(g_lv + (live ? bx : 0u) * 128u), g_rn + (live ? bx : 0u) * 64u);
   }
   wg_sync();
   if (tid == 0)

@@ -593,6 +593,47 @@ def test_the_full_run_of_a_refinement_scan(gpu):
     assert want["full_run_flushes"] == 1
 
 
+def dense_blocks(rng, n):
+    """n blocks whose refinement scan under Al = 1 is long: every even zig-zag position a new coefficient (+-2, a zero in front of each:
+    mostly symbol 0x11, 16 bits in LONG_AC), a quarter of the odd positions a correction bit (+-6)"""
+    z = np.zeros((n, 64), dtype=np.int16)
+    z[:, 2::2] = 2 * rng.choice(np.array([-1, 1]), (n, 31))
+    z[:, 1::2] = 6 * rng.choice(np.array([-1, 1]), (n, 32)) * (rng.random((n, 32)) < 0.25)
+    return z
+
+
+def window_rows():
+    """rows whose chunks need several windows of the coder's 1024-word ring (with LONG_AC, band (1, 63), Al = 1)"""
+    rng = np.random.default_rng(11)
+    dense = dense_blocks(rng, 257)
+    # 246 empty blocks and ten of 63 correction bits each leave a run of 256 open across the chunk seam with 630 buffered bits:
+    # lane 0 of the second chunk emits EOB8 and the buffer in front of a chunk of several windows
+    open_run = _row(256)
+    open_run[246:, 1:] = 6
+    return {"dense": dense, "open run": np.concatenate([open_run, dense_blocks(rng, 257)])}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["dense", "open run"])
+def test_refinement_chunks_of_several_ring_windows(gpu, name):
+    """the refinement coder's window loop, which the rows above (optimal tables) never enter: the chunk of the row's first (dense) or
+    second (open run) 256 blocks holds more than three windows' bytes, as a refinement scan and as a first scan with the point
+    transform.  The serial encoder gives 13,978 / 18,168 bytes (dense: refinement / first) and 14,134 / 19,469 (open run)."""
+    from test_jpeg_progressive import LONG_AC
+    z = window_rows()[name]
+    plane = row_plane(z)
+    dense = z[-257:]
+    for ah in (2, 0):
+        first256 = AE.encode_scan(row_units(dense[:256]), 256, 1, 63, ah, 1, LONG_AC)
+        assert len(first256["segs"][0]) > 3 * 4096, "at least four windows of 1024 words"
+        want = approx_check(gpu, [plane], grey_frame(plane), [0], 1, 63, ah, 1, specs=LONG_AC)
+        assert want["uncoded"] == 0 and want["lost"] == 0
+        if name == "open run" and ah:
+            assert want["max_buffered"] == 630 and want["bit_flushes"] == 0 and want["full_run_flushes"] == 0
+            assert int(want["counts"][0x80]) == 1 and int(want["counts"][0x00]) == 257, "EOB8 for the open run, then a run of one per dense block"
+            assert len(want["segs"][0]) == 14134
+
+
 @pytest.mark.gpu
 def test_sub_ranges_and_pitch_of_refinement_scans(gpu):
     """rows by0..by1 of a call equal the same rows of a full call (both are held to the encoder's), with a pitch wider than the
