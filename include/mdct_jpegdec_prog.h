@@ -84,7 +84,14 @@ int mdct_jpegdec_prog_decode(const mdct_jpegdec_scan *desc, int ss, int se, cons
  *                          The component's ac_slot must be present.
  * interval_status of a refinement interval: as above (exactly the interval's blocks, then 1-bit padding, then RST(k mod 8)); in an AC
  * refinement a symbol of size > 1 is BAD_CODE, a run (a ZRL's sixteen positions included) that ends past se is COEF_OVERFLOW, an
- * EOBn that names more blocks than the interval has left is EOBRUN_OVERFLOW.  A refinement interval that fails touches nothing outside
+ * EOBn that names more blocks than the interval has left is EOBRUN_OVERFLOW.  The first error in decoding order decides, and data
+ * that runs out (or meets a marker) INSIDE a symbol comes before what that symbol would have said: an EOBn whose extra bits are cut
+ * off is OUT_OF_DATA (UNEXPECTED_MARKER at a marker) whether or not the smallest run its code can name would still fit, and so is
+ * a code, a sign bit or a correction bit the data ends in; sixteen bits that are no code are BAD_CODE only where sixteen bits of
+ * data are left.  A lone 0xFF behind the data is a fill byte in front of RSTm and a marker (UNEXPECTED_MARKER) at the end of the
+ * last interval.  A DC refinement interval is judged by its count of data bytes alone: fewer than its blocks' bits is OUT_OF_DATA
+ * (UNEXPECTED_MARKER where a marker cut them short), a whole byte more or a 0-bit in the padding is LEFTOVER.
+ * A refinement interval that fails touches nothing outside
  * the band and the interval's blocks; the blocks it reached hold unspecified refinements, and NOTHING is set back to zero (that
  * would destroy what earlier scans decoded): the caller discards the planes. */
 int mdct_jpegdec_prog_decode_approx(const mdct_jpegdec_scan *desc, int ss, int se, int ah, int al,

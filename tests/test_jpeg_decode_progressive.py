@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import jpeg_decode_checker as DC
+import jpeg_progressive_approx_checker as XC
 import jpeg_progressive_checker as PC
 import jpeg_progressive_encoder as PE
 import jpeg_progressive_status as PS
@@ -395,8 +396,9 @@ def band_mask(ss, se, gx, gy, shape):
     return m
 
 
-def launch(torch, scan, ss, se, specs, comps, mx, my, ri, tables=None):
-    """index + decode of one scan.  comps: [(host plane, h, v, dc_slot, ac_slot)].  -> (planes after, statuses), canaries checked"""
+def launch(torch, scan, ss, se, specs, comps, mx, my, ri, tables=None, ah=0, al=0):
+    """index + decode of one scan.  comps: [(host plane, h, v, dc_slot, ac_slot)].  -> (planes after, statuses), canaries checked.
+    ah, al: successive approximation; a DC refinement scan (ss == 0, ah > 0) reads no table and is given none"""
     from simd_dct_amd import jpeg_decode as D
     planes = [DevPlane(torch, c[0]) for c in comps]
     d = _desc([(p.v.data_ptr(), p.v.stride(0), c[0].shape[1] // 8, c[0].shape[0] // 8, c[1], c[2], c[3], c[4]) for p, c in zip(planes, comps)], mx, my, ri)
@@ -408,10 +410,10 @@ def launch(torch, scan, ss, se, specs, comps, mx, my, ri, tables=None):
     seg = buf[64:64 + max(L, 1)]
     off = torch.full((n + 3,), -1, dtype=torch.int64, device="cuda")
     status = torch.full((n + 2,), -9, dtype=torch.int32, device="cuda")
-    own = tables is None
+    own = tables is None and not (ss == 0 and ah)
     tables = D.Tables(specs) if own else tables
     D.index(seg, n, off[1:n + 2], status[1:n + 1], scan_len=L)
-    D.decode_prog(d, ss, se, tables, seg, off[1:n + 2], status[1:n + 1], scan_len=L)
+    D.decode_prog(d, ss, se, tables, seg, off[1:n + 2], status[1:n + 1], scan_len=L, ah=ah, al=al)
     torch.cuda.synchronize()
     if own:
         tables.close()
@@ -422,34 +424,52 @@ def launch(torch, scan, ss, se, specs, comps, mx, my, ri, tables=None):
     return [p.result() for p in planes], s[1:-1].tolist()
 
 
-def check(torch, scan, ss, se, specs, truths, sampling, mx, my, ri, good=True, slots=None, tables=None):
+def check(torch, scan, ss, se, specs, truths, sampling, mx, my, ri, good=True, slots=None, tables=None, ah=0, al=0, pre=None):
     """Decode `scan` on the GPU into planes that hold a sentinel everywhere but in the band's positions of the blocks the scan covers
     (zero there), one block larger each way than the grid, and compare planes and statuses with jpeg_progressive_status.  good: all
     statuses 0 and the band equals truths (the encoder's input).  sampling: [(h, v)] per component, None for one component over its
-    own grid of mx x my blocks.  -> (planes, statuses)"""
+    own grid of mx x my blocks.  -> (planes, statuses)
+    ah, al: successive approximation.  With either set the truth is jpeg_progressive_approx_checker.decode_scan, run on a copy of
+    what is uploaded.  A refinement scan (ah = al + 1) finds `pre` (a plane per component) in the band's positions in place of the
+    zeros; of a refinement interval that fails only the status is compared: what it leaves in its own blocks' band is unspecified
+    (include/mdct_jpegdec_prog.h), every other block, position and sentinel is compared as ever."""
     one = sampling is None
     samp = [(1, 1)] if one else sampling
     slots = slots or [(min(c, 1), 2 + min(c, 1)) for c in range(len(samp))]
     hosts, masks = [], []
-    for (h, v) in samp:
+    for c, (h, v) in enumerate(samp):
         gx, gy = mx * h, my * v
         host = np.full(((gy + 1) * 8, (gx + 1) * 8), SENT, dtype=np.int16)
         m = band_mask(ss, se, gx, gy, host.shape)
         host[m] = 0
+        if pre is not None:
+            t = np.zeros(host.shape, dtype=np.int16)
+            t[:gy * 8, :gx * 8] = pre[c][:gy * 8, :gx * 8]
+            host[m] = t[m]
         hosts.append(host)
         masks.append(m)
     layout = [(ci, hh, vv, h, v) for ci, (h, v) in enumerate(samp) for vv in range(v) for hh in range(h)]
     if ss == 0:
-        tabs = {ci: DC.code_table(*specs[slots[ci][0]]) for ci in range(len(samp))}
+        tabs = None if ah else {ci: DC.code_table(*specs[slots[ci][0]]) for ci in range(len(samp))}
     else:
         tabs = DC.code_table(*specs[slots[0][1]])
     want = [h.copy() for h in hosts]
-    want_st = PS.decode_scan(scan, ss, se, tabs, PS.block_order(mx, my, layout), ri * len(layout), want)
+    order, per = PS.block_order(mx, my, layout), ri * len(layout)
+    if ah or al:
+        want_st = XC.decode_scan(scan, ss, se, ah, al, tabs, order, per, want)
+    else:
+        want_st = PS.decode_scan(scan, ss, se, tabs, order, per, want)
     got, st = launch(torch, scan, ss, se, specs, [(hosts[c], samp[c][0], samp[c][1], slots[c][0], slots[c][1]) for c in range(len(samp))], mx, my, ri,
-                     tables=tables)
+                     tables=tables, ah=ah, al=al)
     assert st == want_st, (st, want_st)
+    loose = [np.zeros(h.shape, dtype=bool) for h in hosts]  # the band of the blocks of a failed refinement interval
+    if ah:
+        for k, s in enumerate(want_st):
+            for ci, by, bx in order[k * per:(k + 1) * per] if s else ():
+                loose[ci][by * 8:by * 8 + 8, bx * 8:bx * 8 + 8] = True
     for c, (g, w, m) in enumerate(zip(got, want, masks)):
-        assert np.array_equal(g, w), (c, np.argwhere(g != w)[:8].tolist())
+        same = (g == w) | (loose[c] & m)
+        assert same.all(), (c, np.argwhere(~same)[:8].tolist())
         assert (g[~m] == SENT).all(), "outside the band or the grid"
         if good:
             t = np.zeros(g.shape, dtype=np.int16)
