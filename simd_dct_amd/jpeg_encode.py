@@ -98,13 +98,18 @@ def _image_shape(image, layout):
 
 
 def _input_of(image, layout, grey=False):
-    """(pitch, plane stride) of a tensor the front kernels read in place: contiguous innermost dimension, HWC pixels of 3 contiguous bytes"""
+    """(pitch, plane stride) of a tensor the front kernels read in place: contiguous innermost dimension, HWC pixels of 3 contiguous bytes.
+    The stride of a dimension of one element addresses nothing and may be anything (a 1 x 1 image seen through permute or numpy's
+    moveaxis, which both call contiguous): it is taken as the contiguous one."""
+    def step(dim, natural):
+        return natural if image.shape[dim] == 1 else image.stride(dim)
+
     if grey:
-        ok, pitch, stride = image.stride(1) == 1, image.stride(0), 0
+        ok, pitch, stride = step(1, 1) == 1, step(0, image.shape[1]), 0
     elif layout == "HWC":
-        ok, pitch, stride = image.stride(2) == 1 and image.stride(1) == 3, image.stride(0), 0
+        ok, pitch, stride = image.stride(2) == 1 and step(1, 3) == 3, step(0, 3 * image.shape[1]), 0
     else:
-        ok, pitch, stride = image.stride(2) == 1, image.stride(1), image.stride(0)
+        ok, pitch, stride = step(2, 1) == 1, step(1, image.shape[2]), image.stride(0)
     if not ok:
         raise ValueError("image: contiguous innermost dimension (HWC: 3 contiguous bytes per pixel)")
     return pitch, stride

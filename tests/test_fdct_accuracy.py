@@ -598,13 +598,16 @@ def encoder_image(W=203, H=117):
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
-def check_file_against_rule(data, image, sub, grey, interleaved, what):
+def check_file_against_rule(data, image, sub, grey, interleaved, what, decoded=None, min_decided=0.5):
     """the coefficients the decoding checker reads out of `data` against the rule on the encoding checker's planes, padding included,
-    with the file's own DQT as the table -> the coefficient planes"""
+    with the file's own DQT as the table -> the coefficient planes.  decoded: (planes, statuses, dict(frame=..., qtables=[one per
+    component])) of another serial checker in jpeg_decode_checker.decode's form (a progressive file's: tests/jpeg_sweep.py), in place of
+    that checker's own.  min_decided: idct_reference.check_planes' cap (a caller that pools planes of a few blocks hands 0 and applies
+    the cap itself)."""
     import jpeg_decode_checker as DC
     import jpeg_encode_checker as C
     from test_jpeg_encode_optimized import _grid
-    coefs, status, info = DC.decode(data)
+    coefs, status, info = DC.decode(data) if decoded is None else decoded
     frame = info["frame"]
     assert all(s == 0 for st in status for s in st), (what, status)
     H, W = image.shape[:2]
@@ -616,7 +619,7 @@ def check_file_against_rule(data, image, sub, grey, interleaved, what):
         assert p.shape == (ph, pw) and c.shape[0] >= ph and c.shape[1] >= pw
         q = info["qtables"][k]
         try:
-            R.check_planes("fwd_u8", [p], [c[:ph, :pw]], [q])
+            R.check_planes("fwd_u8", [p], [c[:ph, :pw]], [q], min_decided=min_decided)
         except AssertionError as e:
             raise AssertionError(f"{what} component {k}: {e}") from None
     return info["qtables"], coefs
