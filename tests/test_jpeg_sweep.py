@@ -260,17 +260,26 @@ class Engine:
         return self.J.encode_jpeg_batch(images, quality, subsampling, layout)
 
 
+def gpu_block(engine, b):
+    """block b of the committed draw through every check (test_jpeg_hidden_state.py runs the same on poisoned scratch memory)"""
+    JS.run_block(engine, block(b))
+
+
+def gpu_pinned(engine):
+    for seed, k in PINNED:
+        JS.run_case(engine, JS.draw(seed, k), JS.Pool(strict=False))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("b", range(N_BLOCKS))
 def test_gpu_block_of_the_sweep(gpu, b):
-    JS.run_block(gpu, block(b))
+    gpu_block(gpu, b)
 
 
 @pytest.mark.gpu
 def test_gpu_pinned_cases(gpu):
     """the cases the soak found failing, kept; each runs alone, under the soak's rule for the cap"""
-    for seed, k in PINNED:
-        JS.run_case(gpu, JS.draw(seed, k), JS.Pool(strict=False))
+    gpu_pinned(gpu)
 
 
 @pytest.mark.gpu
