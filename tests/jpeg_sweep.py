@@ -4,10 +4,11 @@ tests/test_jpeg_sweep.py runs these over the stand-in on the CPU and over simd_d
   draw(seed, k)     one case, a plain dict, from np.random.default_rng((seed, k)) alone: a picture (size, content, quality, layout,
                     sampling, encoder form), the source of the file that is decoded and transcoded (the case's own encoded file, or a
                     file written from known planes by the test-side encoders), the decode form and the transcode.
+  explicit_case     a case of the same form from stated values, the picture "noisy photo" with it (tests/jpeg_frame_limits.py).
   StandIn           an engine made of test-side pieces only: jpeg_encode_checker.planes, the float64 DCT, rne(. / Q), the test-side
                     entropy encoders; the serial checkers, the float64 IDCT, the colour and scaled checkers; the transform checker.
                     faults=...: one of FAULTS planted in it, which the checks must catch.
-  check_encode / check_decode / check_transcode / check_batches
+  check_encode / check_decode (check_rgb, check_scaled) / check_transcode / check_batches
                     pure functions of bytes and arrays, the truths the suite already trusts.
   run_case / run_block   an engine (StandIn, or the adapter of test_jpeg_sweep.py) through a case / a block of cases with its batches.
   coverage_failures      what the committed draw must contain, stated on the cases.
@@ -196,7 +197,18 @@ def draw(seed, k):
 
 
 def label(case):
-    return f"(seed, k) = ({case['seed']}, {case['k']})"
+    return case.get("name") or f"(seed, k) = ({case['seed']}, {case['k']})"
+
+
+def explicit_case(name, W, H, sampling, form="default", *, picture="noisy photo", picture_seed=0, quality=90, layout="HWC", dc_interleaved=False, scale=2,
+                  transform=None, trim=False, optimize=True, interleaved=False, progressive=False, script=None):
+    """a case of draw()'s form from stated values (tests/jpeg_frame_limits.py): its own file is the source; script: None or 'standard' for the
+    transcode; the encoder's comes with `form`"""
+    assert sampling in ENCODER_SAMPLINGS and form in FORMS and form != "progressive drawn" and script in (None, "standard")
+    return dict(seed=None, k=None, name=name, wide=W > 2000, W=int(W), H=int(H), picture=picture, picture_seed=int(picture_seed), quality=quality, layout=layout,
+                enc_sampling=sampling, form=form, dc_interleaved=bool(dc_interleaved), script=None, source="own", scale=scale,
+                transcode=dict(transform=transform, trim=bool(trim), progressive=bool(progressive), optimize=bool(optimize) or bool(progressive), interleaved=bool(interleaved),
+                               script=script))
 
 
 def source_frame(case):
@@ -278,6 +290,9 @@ def picture(case):
     W, H, n = case["W"], case["H"], len(SAMPLINGS[case["enc_sampling"]])
     if case["picture"] == "flat":
         chans = [np.full((H, W), (case["picture_seed"] + 85 * k) & 255, dtype=np.uint8) for k in range(n)]
+    elif case["picture"] == "noisy photo":  # (no draw takes it: explicit_case's) synth's photo planes, noise of +-16 added
+        chans = [np.clip(synth.plane_u8_np(W, H, "photo", seed=case["picture_seed"] + k).astype(np.int16)
+                         + (synth.plane_u8_np(W, H, "noise", seed=case["picture_seed"] + 10 + k) >> 3) - 16, 0, 255).astype(np.uint8) for k in range(n)]
     else:
         chans = [synth.plane_u8_np(W, H, case["picture"], seed=case["picture_seed"] + k) for k in range(n)]
     return chans[0] if n == 1 else np.stack(chans, axis=-1)
@@ -563,6 +578,10 @@ def check_tables(info, C, optimize, what):
             assert spec_of_codes(sc["huffman"][(1, sc["comps"][0][2])]) == (list(b), list(v)), (what, "AC table of scan", si)
 
 
+PILLOW_MAX = 65500  # libjpeg's JPEG_MAX_DIMENSION: Pillow neither writes nor reads a larger side (T.81 allows 65535); a caller with such a
+# picture says pillow=False to check_encode / check_transcode
+
+
 def check_pillow(data, W, H, grey, what):
     from PIL import Image
     im = Image.open(io.BytesIO(data))
@@ -582,8 +601,8 @@ def expected_scans(W, H, sampling, progressive, script, interleaved):
     return [(tuple(comps), ss, se, ah, al, scan_grid(W, H, sampling, comps)[0]) for comps, ss, se, ah, al in scans]
 
 
-def check_encode(case, data, pic, pool=None):
-    """-> C, the coefficient planes the serial checker reads out of the case's own file"""
+def check_encode(case, data, pic, pool=None, pillow=True):
+    """-> C, the coefficient planes the serial checker reads out of the case's own file.  pillow=False: a side lies above PILLOW_MAX"""
     from test_fdct_accuracy import check_file_against_rule
     what = label(case) + " encode"
     data = bytes(data)
@@ -618,7 +637,8 @@ def check_encode(case, data, pic, pool=None):
     check_scans(data, info, C, expected, what)
     if progressive or kw.get("optimize"):
         check_tables(info, C, True, what)
-    check_pillow(data, W, H, grey, what)
+    if pillow:
+        check_pillow(data, W, H, grey, what)
     return C
 
 
@@ -651,14 +671,23 @@ def check_decode(case, data, C, got, pool=None):
         assert p.shape == (ch, cw) and p.dtype == np.uint8, (what, "plane", ci, p.shape, (ch, cw))
         want, exact, tol = S.component(c, q, 8, cw, ch)
         exact_rule(p, want, exact, tol, R.U8_RANGE, f"{what} plane {ci}", "inverse", c.size // 64, pool)
-    colour = "grey" if len(C) == 1 else "YCbCr"
-    rgb = CC.to_rgb(got["planes"], sampling, W, H, colour)
-    want = rgb if case["layout"] == "HWC" else np.moveaxis(rgb, -1, 0)
-    assert got["rgb"].shape == want.shape and np.array_equal(got["rgb"], want), (what, "RGB", case["layout"], got["rgb"].shape, want.shape)
-    d = case["scale"]
+    check_rgb(what, got["planes"], sampling, W, H, got["rgb"], case["layout"])
+    check_scaled(what, data, C, got["scaled"], case["scale"], pool)
+
+
+def check_rgb(what, planes, sampling, W, H, got, layout):
+    """mode="RGB" is jpeg_color_checker.to_rgb of the engine's own planes, in the layout asked for"""
+    rgb = CC.to_rgb(planes, sampling, W, H, "grey" if len(planes) == 1 else "YCbCr")
+    want = rgb if layout == "HWC" else np.moveaxis(rgb, -1, 0)
+    assert got.shape == want.shape and np.array_equal(got, want), (what, "RGB", layout, got.shape, want.shape)
+
+
+def check_scaled(what, data, C, scaled, d, pool=None):
+    """the planes at 1/d against the scaled rule on the file's true coefficients C"""
+    W, H, sampling, qtables, _ = decoded_frame(data)
     geo, _ = S.geometry(W, H, sampling, d)
-    assert len(got["scaled"]) == len(C), what
-    for ci, (p, c, q, g) in enumerate(zip(got["scaled"], C, qtables, geo)):
+    assert len(scaled) == len(C), what
+    for ci, (p, c, q, g) in enumerate(zip(scaled, C, qtables, geo)):
         assert p.shape == (g[2], g[1]) and p.dtype == np.uint8, (what, f"plane {ci} at 1/{d}", p.shape, (g[2], g[1]))
         want, exact, tol = S.component(c, q, g[0], g[1], g[2])
         exact_rule(p, want, exact, tol, R.U8_RANGE, f"{what} plane {ci} at 1/{d}", f"scaled {g[0]}", c.size // 64, pool)
@@ -668,7 +697,7 @@ def transcode_args(case):
     return dict(case["transcode"])
 
 
-def check_transcode(case, data, C, outcome):
+def check_transcode(case, data, C, outcome, pillow=True):
     """outcome: the file transcode_jpeg returned, or the exception it raised; data, C: the source file and its true planes"""
     what = label(case) + " transcode"
     t = case["transcode"]
@@ -701,7 +730,8 @@ def check_transcode(case, data, C, outcome):
         src = src.reshape(8, 8)
         assert np.array_equal(q.reshape(8, 8), src.T if transposing else src), (what, "DQT of component", ci)
     assert out[2:4] == b"\xff\xe0" and out[6:11] == b"JFIF\x00", (what, "the colour space marker")
-    check_pillow(out, ow, oh, len(osampling) == 1, what)
+    if pillow:
+        check_pillow(out, ow, oh, len(osampling) == 1, what)
     inter = t["interleaved"] and len(osampling) == 3
     expected = expected_scans(ow, oh, osampling, t["progressive"], t["script"], inter)
     whole = not t["progressive"] and inter
@@ -859,12 +889,12 @@ def stage_decode(engine, case, data, C, pool=None):
     check_decode(case, data, C, got, pool)
 
 
-def stage_transcode(engine, case, data, C):
+def stage_transcode(engine, case, data, C, pillow=True):
     try:
         outcome = engine.transcode(data, **transcode_args(case))
     except ValueError as e:  # (what a refusal raises; anything else is the engine's failure and goes up)
         outcome = e
-    check_transcode(case, data, C, outcome)
+    check_transcode(case, data, C, outcome, pillow)
 
 
 class CaseFailure(AssertionError):
